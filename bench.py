@@ -14,10 +14,21 @@ RCCL/xGMI): each rank processes its own independent 512^3 chunk per step
 disjoint outputs are gathered to rank 0 (BASELINE config 3) inside the timed
 region.
 
-Prints ONE JSON line from rank 0 with the whole-job aggregate voxels/sec,
-the blend-kernel roofline (HIP-event timing from the C-ABI profiler), and a
-bounded-sample CPU baseline (the oracle restatement on this box's host
-cores).
+Prints ONE JSON line from rank 0 with the whole-job aggregate voxels/sec
+and `ms_per_step`. A plain run does only that: set up, warm up, time
+`--steps` steps, print.
+
+--full adds everything else the benchmark measures: the blend-kernel and
+conv rooflines (HIP-event timing from the C-ABI profiler, enabled around the
+timed steps) and a bounded-sample CPU baseline (the oracle restatement on
+the host cores). Without --full those two fields are null.
+
+--dump-outputs DIR writes what the last timed step returned on rank 0 (the
+inference output chunk a caller receives) as float32 `DIR/<name>.npy`: a
+fixed strided subsample and a fixed seeded random voxel sample, ~33 MB in
+all for the default workload. The input is a deterministic pattern and the
+weights are seeded, so two builds run with the same arguments can be
+compared output for output.
 """
 import argparse
 import json
@@ -57,12 +68,22 @@ def parse_args():
                    help='identity isolates the tiler/blend path')
     p.add_argument('--dtype', choices=['float32', 'bfloat16'],
                    default='float32')
-    p.add_argument('--no-cpu-baseline', action='store_true')
+    p.add_argument('--full', action='store_true',
+                   help='also measure the kernel rooflines and the CPU '
+                        'baseline (a plain run only times the steps)')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='write a fixed sample of the last timed step\'s '
+                        'output as float32 DIR/<name>.npy')
+    p.add_argument('--no-cpu-baseline', action='store_true',
+                   help='with --full: skip the CPU baseline')
     p.add_argument('--cpu-baseline-seconds', type=float, default=15.0)
     p.add_argument('--cpu-baseline-full', action='store_true',
                    help='run the CPU baseline over ALL patches (no '
                         'extrapolation; ~5-6 min)')
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error('--steps must be at least 1')
+    return args
 
 
 def cpu_baseline(args, chunk_u8: np.ndarray, budget_s: float,
@@ -145,6 +166,40 @@ def read_pmc_traffic(args):
         return None, None
 
 
+DUMP_STRIDED_BYTES = 32 << 20   # cap of the strided subsample
+DUMP_SAMPLE_VOXELS = 2 << 20    # seeded random voxel sample (8 MB)
+
+
+def dump_outputs(dirname: str, out) -> dict:
+    """Write a fixed float32 sample of the step output (the (C, z, y, x)
+    device tensor of the returned chunk) under `dirname`; at most 40 MB.
+
+    output_strided.npy  every s-th voxel along z, y, x (s = the smallest
+                        stride that fits the cap; the whole array if s == 1)
+    output_sample.npy   the voxels at RandomState(0) flat indices
+    """
+    t = out.array
+    if not isinstance(t, torch.Tensor):
+        t = torch.as_tensor(np.asarray(t))
+    t = t.detach()
+    s = 1
+    while t[..., ::s, ::s, ::s].numel() * 4 > DUMP_STRIDED_BYTES:
+        s += 1
+    strided = t[..., ::s, ::s, ::s].to(torch.float32).cpu().numpy()
+    n = min(t.numel(), DUMP_SAMPLE_VOXELS)
+    idx = np.random.RandomState(0).randint(0, t.numel(), size=n,
+                                           dtype=np.int64)
+    idx.sort()
+    sample = t.reshape(-1)[torch.from_numpy(idx).to(t.device)] \
+        .to(torch.float32).cpu().numpy()
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, 'output_strided.npy'),
+            np.ascontiguousarray(strided))
+    np.save(os.path.join(dirname, 'output_sample.npy'), sample)
+    return {'dir': dirname, 'shape': list(t.shape), 'stride': s,
+            'files': ['output_strided.npy', 'output_sample.npy']}
+
+
 def main():
     args = parse_args()
     rank, world = init_distributed()
@@ -212,24 +267,27 @@ def main():
     barrier_sync()
 
     cfx = inferencer.ops.cfx
-    cfx.profile_reset()
-    cfx.profile_enable(True)
-    # the fastconv kernels run on their own context; profile it too
     conv_ctx = None
-    if args.engine == 'rsunet':
-        try:
-            from chunkflow_amd.fastconv import _CTX
-            conv_ctx = _CTX.get(local_rank)
-        except Exception:
-            conv_ctx = None
-    if conv_ctx is not None:
-        conv_ctx.profile_reset()
-        conv_ctx.profile_enable(True)
+    if args.full:
+        cfx.profile_reset()
+        cfx.profile_enable(True)
+        # the fastconv kernels run on their own context; profile it too
+        if args.engine == 'rsunet':
+            try:
+                from chunkflow_amd.fastconv import _CTX
+                conv_ctx = _CTX.get(local_rank)
+            except Exception:
+                conv_ctx = None
+        if conv_ctx is not None:
+            conv_ctx.profile_reset()
+            conv_ctx.profile_enable(True)
 
     barrier_sync()
+    last = None
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = None  # release the previous step's output, as a caller would
+        last = step()
     barrier_sync()
     elapsed = time.perf_counter() - t0
     if world > 1:
@@ -240,15 +298,17 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    blend = cfx.profile_get('blend')
+    blend = None
     # the hand MFMA conv kernels (fastconv) publish FLOPs in the bytes slot
     conv = None
     conv_stream = None
-    if conv_ctx is not None:
-        conv = conv_ctx.profile_get('conv')
-        conv_stream = conv_ctx.profile_get('conv_stream')
-        conv_ctx.profile_enable(False)
-    cfx.profile_enable(False)
+    if args.full:
+        blend = cfx.profile_get('blend')
+        if conv_ctx is not None:
+            conv = conv_ctx.profile_get('conv')
+            conv_stream = conv_ctx.profile_get('conv_stream')
+            conv_ctx.profile_enable(False)
+        cfx.profile_enable(False)
 
     if rank != 0:
         if world > 1:
@@ -258,7 +318,13 @@ def main():
     voxels = float(cz) * cy * cx * world * args.steps
     value = voxels / elapsed
 
-    traffic, traffic_src = read_pmc_traffic(args)
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, last)
+    last = None
+
+    traffic, traffic_src = (read_pmc_traffic(args) if args.full
+                            else (None, None))
     conv_roofline = None
     if conv and conv['count'] > 0 and conv['total_ms'] > 0:
         tflops = conv['bytes'] / (conv['total_ms'] / 1e3) / 1e12
@@ -282,7 +348,7 @@ def main():
                 'kernel': 'upconv/conv155 HBM-stream convs',
             }
     roofline = None
-    if blend['count'] > 0 and blend['total_ms'] > 0:
+    if blend and blend['count'] > 0 and blend['total_ms'] > 0:
         achieved = blend['bytes'] / (blend['total_ms'] / 1e3)
         roofline = {
             'bound': 'hbm',
@@ -300,7 +366,7 @@ def main():
         }
 
     cpu = None
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         cpu = cpu_baseline(args, host_chunk.array,
                            args.cpu_baseline_seconds,
                            full=args.cpu_baseline_full)
@@ -331,8 +397,10 @@ def main():
                         else dist.get_backend())
                        + '-p2p-gather-to-rank0') if world > 1 else None,
         },
+        'full': args.full,
         'roofline': roofline,
         'cpu_baseline': cpu,
+        'dumped_outputs': dumped,
     }
     print(json.dumps(result))
     if world > 1:
