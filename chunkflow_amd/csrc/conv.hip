@@ -1849,7 +1849,7 @@ __global__ __launch_bounds__(512, 1) void k_conv3_zring_bf16_a(
             // (bf16-engine tolerance, not bit-identical to _pl).
             const int gy = y0 + wave;
             const int j = lane & 31;
-            const float bj = bias ? bias[j] : 0.f;
+            const float bj = (bias && j < K) ? bias[j] : 0.f;
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
 #pragma unroll
@@ -2394,7 +2394,7 @@ __global__ __launch_bounds__(512, 1) void k_conv3_zring_bf16_tm(
             // (bf16-engine tolerance, not bit-identical to _pl).
             const int gy = y0 + wave;
             const int j = lane & 31;
-            const float bj = bias ? bias[j] : 0.f;
+            const float bj = (bias && j < K) ? bias[j] : 0.f;
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
 #pragma unroll

@@ -1053,8 +1053,11 @@ def test_sliced_ring_fuzz_shapes():
 @pytest.mark.timeout(600)
 def test_zring_bf16_variant_sweep():
     """Every bf16 ring variant behind CFX_ZRING_PL computes the same conv
-    (vs torch bf16). The env is read once per process, so each variant
-    runs in a subprocess. PL=10 is a timing-only ablation and excluded."""
+    (vs torch bf16), and reproduces the exact-integer fused case of
+    tests/conv_exact_util.py bit for bit vs the f64 CPU conv. The env is
+    read once per process, so each variant runs in a subprocess. PL=10 and
+    PL=12 are timing-only ablations (wrong results by design) and
+    excluded."""
     import subprocess
     import sys
     code = (
@@ -1075,8 +1078,13 @@ def test_zring_bf16_variant_sweep():
         ' conv.bias.to(torch.bfloat16), padding=1) + r).float()\n'
         'got = m._run(x, residual=r, elu=True).float()\n'
         'torch.testing.assert_close(got, want, rtol=0.06, atol=0.06)\n'
+        # exact-integer fused case: bit-equal to the f64 CPU conv
+        'sys.path.insert(0, "tests")\n'
+        'import conv_exact_util as U\n'
+        'for shape in ((2, 4, 11, 35), (1, 3, 18, 67)):\n'
+        '    U.check_c333("bf16", 28, shape, flags=("fused",))\n'
         'print("OK")\n')
-    for pl in ('0', '1', '2', '3', '6', '8', '9', '11', '13'):
+    for pl in ('0', '1', '2', '3', '6', '8', '9', '11', '13', '14', '15'):
         env = dict(os.environ, CFX_ZRING_PL=pl)
         p = subprocess.run([sys.executable, '-c', code], env=env,
                            capture_output=True, text=True, timeout=240,
