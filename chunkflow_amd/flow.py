@@ -365,6 +365,25 @@ def connected_components(tasks, name, input_chunk_name, output_chunk_name,
         yield task
 
 
+@main.command('downsample')
+@click.option('--input-chunk-name', '-i', type=str,
+              default=DEFAULT_CHUNK_NAME, help='input chunk name')
+@click.option('--output-chunk-name', '-o', type=str,
+              default=DEFAULT_CHUNK_NAME, help='output chunk name')
+@click.option('--factor', '-f', type=click.INT, nargs=3, default=(2, 2, 2),
+              help='downsample factor in zyx. The default is 2x2x2.')
+@operator
+def downsample(tasks, input_chunk_name, output_chunk_name, factor):
+    """Downsample a chunk: images are averaged, segmentations are
+    mode-pooled (device chunks stay on the device)."""
+    from .downsample import downsample as _downsample
+    for task in tasks:
+        if task is not None:
+            task[output_chunk_name] = _downsample(task[input_chunk_name],
+                                                  factor)
+        yield task
+
+
 @main.command('plugin')
 @click.option('--name', type=str, default='plugin-1',
               help='name of plugin. Multiple plugins should have different names.')

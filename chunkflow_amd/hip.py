@@ -24,6 +24,8 @@ SYMBOLS = [
     'cfx_crop_margin',
     'cfx_mask_using_last_channel', 'cfx_threshold', 'cfx_nonzero_u8',
     'cfx_connected_components', 'cfx_hist_u8', 'cfx_lut_apply_u8',
+    'cfx_downsample_avg_u8', 'cfx_downsample_avg_f32',
+    'cfx_downsample_mode2', 'cfx_downsample_mode3',
     'cfx_conv3_ndhwc', 'cfx_conv3_ndhwc_w32',
     'cfx_conv3_ndhwc_zring', 'cfx_conv3_ndhwc_bf16',
     'cfx_upconv_2x2', 'cfx_downconv_2x2', 'cfx_conv155_c1',
@@ -316,6 +318,30 @@ class CfxContext:
             ctypes.c_void_p(self.ctx), ctypes.c_void_p(buf_ptr),
             ctypes.c_longlong(n_per_sec), ctypes.c_int(nsec),
             ctypes.c_void_p(lut_ptr)), 'cfx_lut_apply_u8')
+
+    # --- downsample ----------------------------------------------------------
+    def downsample_avg(self, in_ptr, out_ptr, channels, in_dims, factor,
+                       is_f32=False):
+        fn = (self.lib.cfx_downsample_avg_f32 if is_f32
+              else self.lib.cfx_downsample_avg_u8)
+        self._chk(fn(
+            ctypes.c_void_p(self.ctx), ctypes.c_void_p(in_ptr),
+            ctypes.c_void_p(out_ptr), ctypes.c_int(channels), _i3(in_dims),
+            _i3(factor)), 'cfx_downsample_avg')
+
+    def downsample_mode2(self, in_ptr, out_ptr, elem_bytes, in_dims,
+                         preserved_axis):
+        self._chk(self.lib.cfx_downsample_mode2(
+            ctypes.c_void_p(self.ctx), ctypes.c_void_p(in_ptr),
+            ctypes.c_void_p(out_ptr), ctypes.c_int(elem_bytes),
+            _i3(in_dims), ctypes.c_int(preserved_axis)),
+            'cfx_downsample_mode2')
+
+    def downsample_mode3(self, in_ptr, out_ptr, elem_bytes, in_dims):
+        self._chk(self.lib.cfx_downsample_mode3(
+            ctypes.c_void_p(self.ctx), ctypes.c_void_p(in_ptr),
+            ctypes.c_void_p(out_ptr), ctypes.c_int(elem_bytes),
+            _i3(in_dims)), 'cfx_downsample_mode3')
 
     def conv3_ndhwc(self, in_ptr, wgt_ptr, bias_ptr, residual_ptr, out_ptr,
                     n, d, h, w, c, k, do_elu=False, w32=False,

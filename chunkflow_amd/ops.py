@@ -127,6 +127,59 @@ class HipOps:
                                          channels, t.shape[-3:], threshold)
         return out
 
+    def downsample_average(self, t: torch.Tensor, factor) -> torch.Tensor:
+        """Box average of a uint8/float32 (z,y,x) or (C,z,y,x) tensor
+        (semantics: chunkflow_amd/downsample.py)."""
+        from .downsample import check_factor
+        factor = check_factor(factor)
+        if t.dtype not in (torch.uint8, torch.float32):
+            raise TypeError(f'downsample_average: uint8 or float32 only, '
+                            f'but got: {t.dtype}')
+        if t.ndim not in (3, 4):
+            raise ValueError(f'downsample_average: 3-D or 4-D only: {t.shape}')
+        if factor == (1, 1, 1):
+            return t
+        t = t.contiguous()
+        dims = tuple(t.shape[-3:])
+        odims = tuple(-(-s // f) for s, f in zip(dims, factor))
+        out = torch.empty(tuple(t.shape[:-3]) + odims, dtype=t.dtype,
+                          device=t.device)
+        self.cfx.downsample_avg(t.data_ptr(), out.data_ptr(),
+                                1 if t.ndim == 3 else t.shape[0], dims,
+                                factor, is_f32=t.dtype == torch.float32)
+        return out
+
+    def downsample_mode(self, t: torch.Tensor, factor) -> torch.Tensor:
+        """COUNTLESS mode pooling (or the reference's striding fallback) of
+        a 3-D tensor of 4- or 8-byte integer labels."""
+        from .downsample import check_factor, mode_plan
+        if t.ndim != 3:
+            raise ValueError(f'downsample_mode: 3-D only: {t.shape}')
+        if t.is_floating_point() or t.dtype == torch.bool or \
+                t.element_size() not in (4, 8):
+            raise TypeError(f'downsample_mode: 4- or 8-byte integer labels '
+                            f'only, but got: {t.dtype}')
+        plan = mode_plan(t.shape, factor)
+        if plan[0] == 'identity':
+            return t
+        if plan[0] == 'stride':
+            fz, fy, fx = check_factor(factor)
+            return t[::fz, ::fy, ::fx].contiguous()
+        t = t.contiguous()
+        dims = tuple(t.shape)
+        if plan[0] == 'mode2':
+            odims = tuple(s if ax == plan[1] else (s + 1) // 2
+                          for ax, s in enumerate(dims))
+            out = torch.empty(odims, dtype=t.dtype, device=t.device)
+            self.cfx.downsample_mode2(t.data_ptr(), out.data_ptr(),
+                                      t.element_size(), dims, plan[1])
+        else:
+            out = torch.empty(tuple(s // 2 for s in dims), dtype=t.dtype,
+                              device=t.device)
+            self.cfx.downsample_mode3(t.data_ptr(), out.data_ptr(),
+                                      t.element_size(), dims)
+        return out
+
 
 class TorchOps:
     is_hip = False
@@ -196,3 +249,20 @@ class TorchOps:
     def mask_using_last_channel(self, t, threshold):
         keep = t[-1] < threshold
         return t[:-1] * keep
+
+    # CPU plumbing: the host numpy path on the tensor's memory
+    def downsample_average(self, t, factor):
+        from .downsample import average_host
+        if t.dtype not in (torch.uint8, torch.float32):
+            raise TypeError(f'downsample_average: uint8 or float32 only, '
+                            f'but got: {t.dtype}')
+        out = average_host(t.contiguous().numpy(), factor)
+        return torch.from_numpy(np.ascontiguousarray(out))
+
+    def downsample_mode(self, t, factor):
+        from .downsample import mode_host
+        if t.is_floating_point() or t.dtype == torch.bool:
+            raise TypeError(f'downsample_mode: integer labels only, '
+                            f'but got: {t.dtype}')
+        out = mode_host(t.contiguous().numpy(), factor)
+        return torch.from_numpy(np.ascontiguousarray(out))

@@ -129,6 +129,31 @@ int cfx_hist_u8(cfx_ctx* ctx, const unsigned char* in, long long n_per_sec,
 int cfx_lut_apply_u8(cfx_ctx* ctx, unsigned char* buf, long long n_per_sec,
                      int nsec, const unsigned char* lut);
 
+/* ---- downsample (mip pyramid; the reference's downsample operator) ------ */
+/* Box average of a (channels, D, H, W) volume by factor[3] (z,y,x, any
+ * positive ints); out is (channels, ceil(D/fz), ceil(H/fy), ceil(W/fx)).
+ * Edge cells average the voxels that exist. Bit-pinned to the reference's
+ * lib/igneous/downsample.py: f32 sum from 0 with x-offset slowest and
+ * z-offset fastest, f64 quotient sum/count, then round-to-nearest (f32) or
+ * truncation (u8). Factors in {1,2} on 16-byte-aligned rows take a vector
+ * path. */
+int cfx_downsample_avg_u8(cfx_ctx* ctx, const unsigned char* in,
+                          unsigned char* out, int channels,
+                          const int in_dims[3], const int factor[3]);
+int cfx_downsample_avg_f32(cfx_ctx* ctx, const float* in, float* out,
+                           int channels, const int in_dims[3],
+                           const int factor[3]);
+/* COUNTLESS 2D mode pooling of a (D, H, W) label volume: 2x2 over the two
+ * axes other than preserved_axis (0=z, 1=y, 2=x). elem_bytes is 4 or 8;
+ * labels compare as raw bit patterns. A pooled axis of odd length n is
+ * front-mirrored ([v0,v0,v1,..]), so its output length is (n+1)/2. */
+int cfx_downsample_mode2(cfx_ctx* ctx, const void* in, void* out,
+                         int elem_bytes, const int in_dims[3],
+                         int preserved_axis);
+/* COUNTLESS 3D mode pooling, 2x2x2; every dimension must be even */
+int cfx_downsample_mode3(cfx_ctx* ctx, const void* in, void* out,
+                         int elem_bytes, const int in_dims[3]);
+
 /* ---- hand-written MFMA convolution (RSUNet ResBlock 3x3x3) -------------- */
 /* NDHWC f32, stride 1, pad 1, C == K in {28, 36, 48, 64}; wgt layout
  * (27, C, K) with tap = ((dz+1)*3 + (dy+1))*3 + (dx+1); bias may be NULL;
