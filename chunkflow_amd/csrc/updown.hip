@@ -343,136 +343,226 @@ __global__ __launch_bounds__(256, 2) void k_conv155_c1(
     }
 }
 
-// ---- output conv (1,5,5), pad (0,2,2), few output channels ---------------
-// RSUNet's conv_out (28 -> 3). MIOpen's bf16 implicit GEMM degenerates on
-// the K=3 output dim (measured 38.6 ms per batch-24 launch). Thread =
-// one output position computing all K: 5 input rows staged to LDS in the
-// raw dtype, weights [K][25][28-padded] f32 in LDS, f32 accumulation.
-template <typename T, int XI, int CC, int KO, int MODE = 0>
-__global__ __launch_bounds__(256, 2) void k_conv155_out(
-    const T* __restrict__ in, const T* __restrict__ wgt,
-    const float* __restrict__ bias, T* __restrict__ out, int N, int D,
-    int H, int W) {
-    // One WG = 4 output rows x XI x-positions: the 8 staged input rows
-    // are shared by the 4 rows (2 LDS rows per output instead of 5 --
-    // the single-row version was LDS-bound at 1 WG/CU and latency-bound).
-    // 256 threads = 4 waves, wave = local y; lane covers 2 x positions.
-    __shared__ T s_in[8][XI + 4][CC];
-    __shared__ float s_w[KO][25][28];     // c rows padded to 28 (16 B)
+// ---- output conv (1,5,5), pad (0,2,2), 28 -> 3 channels, on the MFMA -----
+// RSUNet's conv_out. N = 3 output channels would waste a 16-wide matrix
+// tile, so the five x-taps are folded into the output dimension: for an
+// output row y and staged positions x' the GEMM is
+//   P[x'][j] = sum_{dy,c} in[y+dy-2][x'][c] * w[k][dy][dx][c],  j = dx*3+k
+// (M = x', N = 15 real columns + one zero column, K = 5*28 = 140 = 35
+// steps of v_mfma_f32_16x16x4_f32), and the output is the shifted sum
+//   out[y][x][k] = bias[k] + sum_dx P[x+dx-2][dx*3+k].
+//
+// Tiling (chosen: fixed tiles, no persistent y-walk). One workgroup =
+// CO_R = 6 output rows x CO_S = 60 output positions: it stages 10 input
+// rows x 64 positions (x' = x0-2 .. x0+61, so both 2-column halos come
+// from the workgroup's own strip) in the raw dtype, [row][x][c] with c
+// stride 28. f32: 71,680 B of LDS -> 2 workgroups per CU (2 waves per
+// SIMD); bf16: 35,840 B -> 4. Wave w owns the 16-position tile w for all
+// 6 rows: an A fragment (lane (i, kk) reads in[row][16w+i][4s+kk]) is read
+// once per staged row and feeds the up-to-5 output rows it is a dy tap
+// of, i.e. 7 LDS reads per 35 MFMAs, and the 6 row accumulators are
+// independent MFMA chains. The 35 B fragments (packed by the host as
+// [dy*7+s][lane], lane = kk*16 + j) live in 35 VGPRs, loaded once.
+// The shifted sum crosses lanes: P is bounced through LDS (over the
+// input tile, [row][j][x'] with a 72-dword j stride so the b128 writes
+// and reads spread over the banks); 90 threads then each produce 4
+// consecutive positions x 3 channels = 12 contiguous outputs (3 x 16 B
+// in f32, 3 x 8 B in bf16, when W % 4 == 0 and `out` is 16 B aligned;
+// scalar stores otherwise).
+// Cost of the fixed tiles: every staged row is read (6+4)/6 = 1.67x and
+// every column 64/60 = 1.07x, 1.78x together (the repeats are L2 hits
+// between neighbouring workgroups). x-waste at W = 256: 5 strips, the
+// last holds 16 outputs and runs 2 of its 4 tiles, so 18 MFMA tiles for
+// 16 tiles of output = 12.5 % over, on top of the 16/15 zero column.
+// f32 accumulation, bf16 rounded once at the store.
+constexpr int CO_R = 6;    // output rows per workgroup
+constexpr int CO_S = 60;   // output positions per workgroup (64 staged)
+constexpr int CO_PS = 72;  // P bounce: dwords between j rows
+
+typedef float co_f32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ unsigned short bf16_bits(float v) {
+    return ((__hip_bfloat16_raw)__float2bfloat16(v)).x;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256, 2) void k_conv155_out_mfma(
+    const T* __restrict__ in, const float* __restrict__ wfrag,
+    const float* __restrict__ bias, T* __restrict__ out, int H, int W,
+    int vec_ok) {
+    constexpr int RS = CO_R + 4;           // staged rows
+    constexpr int XS = 64;                 // staged positions
+    constexpr int CC = 28, C4 = CC / 4;
+    constexpr int NV = RS * XS * C4;       // 4-channel vectors to stage
+    constexpr int PER = (NV + 255) / 256;  // per thread
+    constexpr int BATCH = 6;               // loads in flight per thread
+    static_assert(CO_R * 16 * CO_PS * 4 <= RS * XS * CC * (int)sizeof(T),
+                  "P bounce must fit over the input tile");
+    __shared__ __attribute__((aligned(16))) T s_in[RS * XS * CC];
+    float* s_p = reinterpret_cast<float*>(s_in);  // after the MFMA phase
+
     const int tid = threadIdx.x;
     const int wave = tid >> 6;
     const int lane = tid & 63;
-    const int nz = blockIdx.z;
-    const int y0 = blockIdx.y * 4;
-    const int x0 = blockIdx.x * XI;
+    const int y0 = blockIdx.y * CO_R;
+    const int x0 = blockIdx.x * CO_S;
+    const long long plane = (long long)blockIdx.z * H;
+    const int nout = min(CO_S, W - x0);      // valid outputs of this strip
+    const int ntile = (nout + 4 + 15) >> 4;  // 16-position tiles needed
 
-    const long long plane = (long long)nz * H;
-    const int C4 = CC / 4;
+    float b[35];
+#pragma unroll
+    for (int s = 0; s < 35; ++s) b[s] = wfrag[s * 64 + lane];
+
+    // stage: batched so the global loads pipeline; zero outside the image
     typedef typename vec4<T>::type tx4;
-    for (int idx = tid; MODE != 2 && idx < 8 * (XI + 4) * C4;
-         idx += 256) {
-        const int c4 = idx % C4;
-        const int xl = (idx / C4) % (XI + 4);
-        const int r = idx / (C4 * (XI + 4));
-        const int gy = y0 + r - 2;
-        const int gx = x0 + xl - 2;
-        const bool ok = gy >= 0 && gy < H && gx >= 0 && gx < W;
-        *reinterpret_cast<tx4*>(&s_in[r][xl][c4 * 4]) =
-            ok ? *reinterpret_cast<const tx4*>(
-                     &in[((plane + gy) * W + gx) * (long long)CC + c4 * 4])
-               : tx4{};
-    }
-    for (int idx = tid; MODE != 2 && idx < KO * 25 * 28; idx += 256) {
-        const int c = idx % 28;
-        const int t = (idx / 28) % 25;
-        const int k = idx / (28 * 25);
-        s_w[k][t][c] = c < CC ? ldf(&wgt[(k * 25 + t) * CC + c]) : 0.f;
+#pragma unroll 1
+    for (int b0 = 0; b0 < PER; b0 += BATCH) {
+        tx4 v[BATCH];
+#pragma unroll
+        for (int u = 0; u < BATCH; ++u) {
+            const int idx = (b0 + u) * 256 + tid;
+            const int r = idx / (XS * C4);
+            const int rem = idx - r * (XS * C4);
+            const int xl = rem / C4;
+            const int c4 = rem - xl * C4;
+            const int gy = y0 + r - 2;
+            const int gx = x0 + xl - 2;
+            const bool ok = b0 + u < PER && idx < NV && gy >= 0 &&
+                            gy < H && gx >= 0 && gx < W &&
+                            xl < ntile * 16;
+            v[u] = ok ? *reinterpret_cast<const tx4*>(
+                            &in[((plane + gy) * W + gx) * (long long)CC +
+                                c4 * 4])
+                      : tx4{};
+        }
+#pragma unroll
+        for (int u = 0; u < BATCH; ++u) {
+            const int idx = (b0 + u) * 256 + tid;
+            if (b0 + u < PER && idx < NV)
+                *reinterpret_cast<tx4*>(&s_in[idx * 4]) = v[u];
+        }
     }
     __syncthreads();
 
-    const int y = y0 + wave;
-    if (y >= H) return;
-    float acc[2][KO];
+    // MFMA phase: A[i = lane&15][k = lane>>4], B[k = lane>>4][j = lane&15]
+    co_f32x4 acc[CO_R];
 #pragma unroll
-    for (int p = 0; p < 2; ++p)
+    for (int y = 0; y < CO_R; ++y) acc[y] = co_f32x4{0.f, 0.f, 0.f, 0.f};
+    if (wave < ntile) {
+        const T* abase = &s_in[(wave * 16 + (lane & 15)) * CC + (lane >> 4)];
 #pragma unroll
-        for (int k = 0; k < KO; ++k) acc[p][k] = bias ? bias[k] : 0.f;
-#pragma unroll 1
-    for (int tap = 0; tap < 25 && MODE != 1; ++tap) {  // MODE 1: skip
-        const int dy = tap / 5, dx = tap % 5;
-        // unroll 2 gives the dependent LDS reads cross-iteration ILP
-        // (full unroll hoists 7x3 float4 weight reads and spills)
-#pragma unroll 2
-        for (int c4 = 0; c4 < C4; ++c4) {
-            float4 w4k[KO];
+        for (int r = 0; r < RS; ++r) {
+            float a[C4];
 #pragma unroll
-            for (int k = 0; k < KO; ++k)
-                w4k[k] = *reinterpret_cast<const float4*>(
-                    &s_w[k][tap][c4 * 4]);
+            for (int s = 0; s < C4; ++s)
+                a[s] = cvf(abase[r * XS * CC + s * 4]);
 #pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                const tx4 v4 = *reinterpret_cast<const tx4*>(
-                    &s_in[wave + dy][lane * 2 + p + dx][c4 * 4]);
-                const float f0 = vec4<T>::get(v4, 0);
-                const float f1 = vec4<T>::get(v4, 1);
-                const float f2 = vec4<T>::get(v4, 2);
-                const float f3 = vec4<T>::get(v4, 3);
+            for (int s = 0; s < C4; ++s)
 #pragma unroll
-                for (int k = 0; k < KO; ++k)
-                    acc[p][k] += f0 * w4k[k].x + f1 * w4k[k].y +
-                                 f2 * w4k[k].z + f3 * w4k[k].w;
-            }
+                for (int dy = 0; dy < 5; ++dy) {
+                    const int y = r - dy;  // staged row r is tap dy of y
+                    if (y >= 0 && y < CO_R)
+                        acc[y] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                            a[s], b[dy * C4 + s], acc[y], 0, 0, 0);
+                }
         }
     }
+    __syncthreads();  // every A read done: the tile becomes the P bounce
+
+    // D[row = (lane>>4)*4 + reg][col = lane&15] -> s_p[y][j][x']
+    if (wave < ntile) {
 #pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        const int gx = x0 + lane * 2 + p;
-        if (gx >= W) continue;
-        T* op =
-            out + (plane + y) * (long long)W * KO + (long long)gx * KO;
+        for (int y = 0; y < CO_R; ++y)
+            *reinterpret_cast<co_f32x4*>(
+                &s_p[(y * 16 + (lane & 15)) * CO_PS + wave * 16 +
+                     (lane >> 4) * 4]) = acc[y];
+    }
+    __syncthreads();
+
+    // shifted sum: thread = (row, 4 consecutive positions), 12 outputs
+    if (tid >= CO_R * (CO_S / 4)) return;
+    const int yl = tid / (CO_S / 4);
+    const int q = tid - yl * (CO_S / 4);
+    const int y = y0 + yl;
+    const int gx = x0 + q * 4;
+    if (y >= H || gx >= W) return;
+    float o[4][3];
 #pragma unroll
-        for (int k = 0; k < KO; ++k) stf(&op[k], acc[p][k]);
+    for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) o[e][k] = bias ? bias[k] : 0.f;
+#pragma unroll
+    for (int j = 0; j < 15; ++j) {
+        const int dx = j / 3, k = j % 3;
+        const float* pr = &s_p[(yl * 16 + j) * CO_PS + q * 4];
+        const co_f32x4 lo = *reinterpret_cast<const co_f32x4*>(pr);
+        const co_f32x4 hi = *reinterpret_cast<const co_f32x4*>(pr + 4);
+        const float p8[8] = {lo[0], lo[1], lo[2], lo[3],
+                             hi[0], hi[1], hi[2], hi[3]};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e][k] += p8[e + dx];
+    }
+    T* op = out + ((plane + y) * W + gx) * 3LL;
+    if (vec_ok) {  // W % 4 == 0: the 4 positions exist and op is aligned
+        if (sizeof(T) == 2) {
+            typedef unsigned co_u32x2 __attribute__((ext_vector_type(2)));
+            unsigned short h[12];
+#pragma unroll
+            for (int i = 0; i < 12; ++i) h[i] = bf16_bits(o[i / 3][i % 3]);
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                co_u32x2 u;
+                u.x = h[4 * i] | ((unsigned)h[4 * i + 1] << 16);
+                u.y = h[4 * i + 2] | ((unsigned)h[4 * i + 3] << 16);
+                reinterpret_cast<co_u32x2*>(op)[i] = u;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                co_f32x4 f;
+#pragma unroll
+                for (int m = 0; m < 4; ++m)
+                    f[m] = o[(4 * i + m) / 3][(4 * i + m) % 3];
+                reinterpret_cast<co_f32x4*>(op)[i] = f;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (gx + e < W)
+#pragma unroll
+                for (int k = 0; k < 3; ++k) stf(&op[e * 3 + k], o[e][k]);
     }
 }
 
 }  // namespace
 
 extern "C" int cfx_conv155_out(cfx_ctx* ctx, const void* in,
-                               const void* wgt, const float* bias,
+                               const float* wfrag, const float* bias,
                                void* out, int N, int D, int H, int W,
                                int C, int K, int is_bf16) {
     if (C != 28 || K != 3) {
         g_err = "cfx_conv155_out: only C == 28, K == 3 instantiated";
         return -1;
     }
+    if ((long long)N * D > 65535) {
+        g_err = "cfx_conv155_out: N * D <= 65535 supported";
+        return -1;
+    }
     hipEvent_t e0;
     if (prof_begin(ctx, &e0)) return -1;
-    constexpr int XI = 128;  // wave covers 2*64 x; 4 rows per WG
-    dim3 grid((W + XI - 1) / XI, (H + 3) / 4, (unsigned)(N * D));
-    static const int om = [] {
-        const char* e = getenv("CFX_CONVOUT_MODE");  // timing ablation
-        return e ? atoi(e) : 0;
-    }();
-    if (is_bf16 && om == 1)
-        hipLaunchKernelGGL((k_conv155_out<cfx_bf16, XI, 28, 3, 1>), grid,
-                           dim3(256), 0, ctx->stream, (const cfx_bf16*)in,
-                           (const cfx_bf16*)wgt, bias, (cfx_bf16*)out, N,
-                           D, H, W);
-    else if (is_bf16 && om == 2)
-        hipLaunchKernelGGL((k_conv155_out<cfx_bf16, XI, 28, 3, 2>), grid,
-                           dim3(256), 0, ctx->stream, (const cfx_bf16*)in,
-                           (const cfx_bf16*)wgt, bias, (cfx_bf16*)out, N,
-                           D, H, W);
-    else if (is_bf16)
-        hipLaunchKernelGGL((k_conv155_out<cfx_bf16, XI, 28, 3>), grid,
-                           dim3(256), 0, ctx->stream, (const cfx_bf16*)in,
-                           (const cfx_bf16*)wgt, bias, (cfx_bf16*)out, N,
-                           D, H, W);
+    dim3 grid((W + CO_S - 1) / CO_S, (H + CO_R - 1) / CO_R,
+              (unsigned)(N * D));
+    const int vec_ok = W % 4 == 0 && ((size_t)out & 15) == 0;
+    if (is_bf16)
+        hipLaunchKernelGGL((k_conv155_out_mfma<cfx_bf16>), grid, dim3(256),
+                           0, ctx->stream, (const cfx_bf16*)in, wfrag, bias,
+                           (cfx_bf16*)out, H, W, vec_ok);
     else
-        hipLaunchKernelGGL((k_conv155_out<float, XI, 28, 3>), grid,
-                           dim3(256), 0, ctx->stream, (const float*)in,
-                           (const float*)wgt, bias, (float*)out, N, D, H,
-                           W);
+        hipLaunchKernelGGL((k_conv155_out_mfma<float>), grid, dim3(256), 0,
+                           ctx->stream, (const float*)in, wfrag, bias,
+                           (float*)out, H, W, vec_ok);
     CFX_CHECK(hipGetLastError());
     double flops = 2.0 * 25.0 * C * K * (double)N * D * H * W;
     if (prof_end(ctx, e0, CFX_K_CONV_STREAM, flops)) return -1;

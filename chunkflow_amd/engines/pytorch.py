@@ -69,8 +69,8 @@ class PyTorchEngine(EngineBase):
                     self.model, idx, bf16=bf)
                 self.fastconv_count += accelerate_conv_in(
                     self.model, idx, bf16=bf)
-                # conv_out kernel beats MIOpen at both dtypes (4.8x bf16,
-                # 1.4x f32 -- profiles/updown_probe_r02.json)
+                # conv_out kernel beats MIOpen at both dtypes (13.6x bf16,
+                # 5.2x f32 -- profiles/convout_mfma.json)
                 from ..fastconv import accelerate_conv_out
                 self.fastconv_count += accelerate_conv_out(
                     self.model, idx, bf16=bf)

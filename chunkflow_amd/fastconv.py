@@ -462,21 +462,29 @@ def accelerate_conv_in(model: nn.Module, device_index: int = 0,
 
 
 class CfxConvOut155(nn.Module):
-    """Drop-in for nn.Conv3d(C, K<=3-ish, (1,5,5), padding=(0,2,2)) — the
+    """Drop-in for nn.Conv3d(28, 3, (1,5,5), padding=(0,2,2)) — the
     RSUNet output conv. MIOpen's bf16 implicit GEMM degenerates on the
-    tiny K (measured 38.6 ms per batch-24 launch vs ~2 ms here)."""
+    tiny K (measured 38.6 ms per batch-24 launch vs 2.85 ms here;
+    f32 at batch 12 x 20: 6.76 ms vs 1.29 ms, profiles/convout_mfma.json).
+    28 -> 3 only: the five x-taps are folded into the MFMA's output
+    dimension (csrc/updown.hip)."""
 
     def __init__(self, conv: nn.Conv3d, device_index: int = 0,
                  bf16: bool = False):
         super().__init__()
         self.C = conv.in_channels
         self.K = conv.out_channels
+        assert (self.C, self.K) == (28, 3), 'conv_out kernel is 28 -> 3'
         self.device_index = device_index
         self.bf16 = bf16
         w = conv.weight.detach().float()      # (K, C, 1, 5, 5)
-        pack = w[:, :, 0].permute(0, 2, 3, 1).reshape(self.K, 25, self.C)
-        dt = torch.bfloat16 if bf16 else torch.float32
-        self.register_buffer('wpack', pack.to(dt).contiguous())
+        if bf16:                              # the kernel multiplies in f32
+            w = w.to(torch.bfloat16).float()
+        # B fragments of the 35 K-steps: [dy*7 + c//4][(c%4)*16 + j] with
+        # j = dx*3 + k and a zero 16th column
+        pack = w[:, :, 0].permute(2, 1, 3, 0).reshape(5, 28, 15)
+        pack = torch.nn.functional.pad(pack, (0, 1)).reshape(35, 64)
+        self.register_buffer('wpack', pack.contiguous())
         if conv.bias is not None:
             self.register_buffer('bias', conv.bias.detach().float())
         else:
@@ -487,6 +495,7 @@ class CfxConvOut155(nn.Module):
         n, c, d, h, w = x.shape
         dt = torch.bfloat16 if self.bf16 else torch.float32
         assert x.dtype == dt and c == self.C
+        assert self.wpack.dtype == torch.float32
         out = torch.empty((n, self.K, d, h, w), dtype=dt, device=x.device,
                           memory_format=torch.channels_last_3d)
         get_cfx(self.device_index).conv155_out(
@@ -505,8 +514,9 @@ def _conv155_out_eligible(m) -> bool:
 
 def accelerate_conv_out(model: nn.Module, device_index: int = 0,
                         bf16: bool = False) -> int:
-    """Swap the eligible few-channel (1,5,5) output convs (bf16 wins big;
-    f32 MIOpen is already fine there — callers gate)."""
+    """Swap the eligible 28 -> 3 (1,5,5) output convs for the MFMA kernel;
+    returns count. It beats MIOpen at both dtypes
+    (profiles/convout_mfma.json), so callers swap unconditionally."""
     count = 0
     dev = f'cuda:{device_index}'
     for parent in list(model.modules()):

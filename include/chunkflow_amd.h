@@ -197,9 +197,12 @@ int cfx_conv155_c1(cfx_ctx* ctx, const void* in, const void* wgt,
                    const float* bias, void* out, int N, int D, int H,
                    int W, int K, int is_bf16);
 /* few-output-channel (1,5,5) conv, pad (0,2,2) — RSUNet conv_out; in
- * (N,D,H,W,C), out (N,D,H,W,K) NDHWC; wgt [K][25][C] (k, dy*5+dx, c) in
- * the compute dtype; C == 28, K == 3 instantiated */
-int cfx_conv155_out(cfx_ctx* ctx, const void* in, const void* wgt,
+ * (N,D,H,W,C), out (N,D,H,W,K) NDHWC, any N, D, H, W >= 1 with
+ * N*D <= 65535; C == 28, K == 3 instantiated. wfrag is always f32 (for
+ * bf16 the values are pre-rounded to bf16), packed as the 35 MFMA B
+ * fragments [dy*7 + c/4][lane = (c%4)*16 + j], j = dx*3 + k, column
+ * j == 15 zero: 35*64 floats */
+int cfx_conv155_out(cfx_ctx* ctx, const void* in, const float* wfrag,
                     const float* bias, void* out, int N, int D, int H,
                     int W, int C, int K, int is_bf16);
 /* the 32x32x2-MFMA variant (C == K == 28 instantiated) */
