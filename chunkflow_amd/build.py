@@ -10,6 +10,7 @@ SRC_IMG = os.path.join(PKG_DIR, 'csrc', 'image.hip')
 SRC_CONV = os.path.join(PKG_DIR, 'csrc', 'conv.hip')
 SRC_UPDOWN = os.path.join(PKG_DIR, 'csrc', 'updown.hip')
 SRC_DOWNSAMPLE = os.path.join(PKG_DIR, 'csrc', 'downsample.hip')
+SRC_LABELS = os.path.join(PKG_DIR, 'csrc', 'labels.hip')
 SRC_INT = os.path.join(PKG_DIR, 'csrc', 'cfx_internal.h')
 HEADER = os.path.join(PKG_DIR, '..', 'include', 'chunkflow_amd.h')
 
@@ -20,7 +21,7 @@ def so_is_fresh() -> bool:
     so_mtime = os.path.getmtime(SO_PATH)
     return all(os.path.getmtime(p) <= so_mtime
                for p in (SRC, SRC_CC, SRC_IMG, SRC_CONV, SRC_UPDOWN,
-                         SRC_DOWNSAMPLE, SRC_INT, HEADER))
+                         SRC_DOWNSAMPLE, SRC_LABELS, SRC_INT, HEADER))
 
 
 def build(force: bool = False) -> str:
@@ -34,7 +35,7 @@ def build(force: bool = False) -> str:
     cmd = [
         'hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17',
         '-ffp-contract=off', '-fPIC', '-shared', SRC, SRC_CC, SRC_IMG,
-        SRC_CONV, SRC_UPDOWN, SRC_DOWNSAMPLE, '-o', SO_PATH,
+        SRC_CONV, SRC_UPDOWN, SRC_DOWNSAMPLE, SRC_LABELS, '-o', SO_PATH,
     ]
     subprocess.run(cmd, check=True)
     return SO_PATH

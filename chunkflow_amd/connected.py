@@ -11,11 +11,15 @@ exactly (min-index roots ranked in flat order; csrc/cc.hip).
 Device chunks run the gfx950 union-find; host chunks use scipy. With a
 threshold both implement the binary semantics (threshold > t). Without a
 threshold the reference's cc3d keeps EQUAL-VALUE semantics (each connected
-region of one value is one component; 0 is background) — implemented here
-as `equal_value_label` (per-value scipy labeling renumbered in raster-scan
+region of one value is one component; 0 is background). On the host that is
+`equal_value_label` (per-value scipy labeling renumbered in raster-scan
 first-encounter order; cc3d's own numbering/dtype is implementation-defined
-and unpinned). A multi-valued device chunk without a
-threshold falls back to the host path (correctness over speed; warned).
+and unpinned). On the device an integer chunk of 1-, 4- or
+8-byte voxels runs the same union-find with a "values equal" predicate
+(cfx_connected_components_labels; values compare as raw bit patterns) and
+produces the same labels as `equal_value_label`, as an int32 tensor carrying
+uint32 labels like the binary path. Only a FLOAT device chunk without a
+threshold still takes the host path (warned).
 """
 import warnings
 import numpy as np
@@ -74,22 +78,32 @@ def connected_component_gpu(chunk: Chunk, threshold: float = None,
     t3 = _first_channel(t).contiguous()
     dims = tuple(t3.shape)
     n = t3.numel()
+    labels = torch.empty(dims, dtype=torch.int32, device=t3.device)
+    scratch = torch.empty(dims, dtype=torch.int32, device=t3.device)
+    if threshold is None and _is_label_dtype(t3):
+        # equal-value semantics straight on the label volume
+        ops.cfx.connected_components_labels(
+            t3.data_ptr(), t3.element_size(), dims, connectivity,
+            labels.data_ptr(), scratch.data_ptr())
+        return Chunk(labels, voxel_offset=chunk.voxel_offset,
+                     voxel_size=chunk.voxel_size)
     fg = torch.empty(dims, dtype=torch.uint8, device=t3.device)
     if threshold is not None:
         if t3.dtype != torch.float32:
             t3 = t3.to(torch.float32)
         ops.cfx.threshold(t3.data_ptr(), fg.data_ptr(), n, float(threshold))
     else:
-        if t3.dtype == torch.uint8:
-            ops.cfx.nonzero_u8(t3.data_ptr(), fg.data_ptr(), n)
-        else:
-            fg = (t3 != 0).to(torch.uint8).contiguous()
-    labels = torch.empty(dims, dtype=torch.int32, device=t3.device)
-    scratch = torch.empty(dims, dtype=torch.int32, device=t3.device)
+        fg = (t3 != 0).to(torch.uint8).contiguous()
     ops.cfx.connected_components(fg.data_ptr(), dims, connectivity,
                                  labels.data_ptr(), scratch.data_ptr())
     return Chunk(labels, voxel_offset=chunk.voxel_offset,
                  voxel_size=chunk.voxel_size)
+
+
+def _is_label_dtype(t) -> bool:
+    """An integer tensor the equal-value kernel takes as it is."""
+    return (not t.is_floating_point() and not t.is_complex()
+            and t.dtype != torch.bool and t.element_size() in (1, 4, 8))
 
 
 def _is_multivalued(arr3) -> bool:
@@ -105,12 +119,16 @@ def connected_component(chunk: Chunk, threshold: float = None,
                         connectivity: int = 6) -> Chunk:
     assert connectivity in _STRUCTS
     if chunk.is_device:
-        if threshold is None and _is_multivalued(_first_channel(chunk.array)):
-            # cc3d equal-value semantics; no GPU kernel for it yet — the
-            # binary union-find would merge touching different-label regions
+        arr3 = _first_channel(chunk.array)
+        if threshold is None and not _is_label_dtype(arr3) \
+                and _is_multivalued(arr3):
+            # cc3d equal-value semantics on float (or 2-byte) voxels: the
+            # device kernel takes 1-, 4- and 8-byte integers only, and the
+            # binary union-find would merge touching different-value regions
             warnings.warn('connected-components without --threshold on a '
-                          'multi-valued device chunk: falling back to the '
-                          'host equal-value path (cc3d semantics)')
+                          'multi-valued non-integer device chunk: falling '
+                          'back to the host equal-value path (cc3d '
+                          'semantics)')
             c = chunk.numpy()
             labels = equal_value_label(
                 np.ascontiguousarray(_first_channel(c.array)), connectivity)

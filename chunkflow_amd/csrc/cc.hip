@@ -11,6 +11,11 @@
 // (per-chunk root counts -> host exclusive scan of the small count array ->
 // wave-ballot local ranks), and a final gather. All buffers are
 // caller-owned except the small per-chunk count array (context scratch).
+//
+// Which neighbours belong together is a predicate the kernels are templated
+// on: BinaryFg (a u8 foreground mask; any two foreground neighbours unite)
+// or EqualValue<T> (a label volume; non-zero neighbours unite iff their raw
+// bit patterns are equal — cc3d's multi-label semantics).
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -91,23 +96,44 @@ __device__ inline void cc_union(unsigned int* __restrict__ p,
     }
 }
 
-__global__ void k_cc_init(const unsigned char* __restrict__ fg,
-                          unsigned int* __restrict__ parent, long long n) {
+// "same component?" predicates: v is the voxel array, fg() tells foreground
+// from a voxel's value, same() whether a FOREGROUND voxel of value a unites
+// with a neighbour of value b
+struct BinaryFg {
+    const unsigned char* __restrict__ v;
+    __device__ static bool fg(unsigned char a) { return a != 0; }
+    __device__ static bool same(unsigned char, unsigned char b) {
+        return b != 0;
+    }
+};
+
+template <typename T>
+struct EqualValue {
+    const T* __restrict__ v;
+    __device__ static bool fg(T a) { return a != 0; }
+    // a != 0 here, so a == b also makes the neighbour foreground
+    __device__ static bool same(T a, T b) { return a == b; }
+};
+
+template <typename P>
+__global__ void k_cc_init(P pred, unsigned int* __restrict__ parent,
+                          long long n) {
     long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
     long long stride = gridDim.x * (long long)blockDim.x;
     for (; i < n; i += stride)
         cc_st(parent, (unsigned int)i,
-              fg[i] ? (unsigned int)i : 0xFFFFFFFFu);
+              P::fg(pred.v[i]) ? (unsigned int)i : 0xFFFFFFFFu);
 }
 
-__global__ void k_cc_merge(const unsigned char* __restrict__ fg,
-                           unsigned int* __restrict__ parent, int D, int H,
-                           int W, int ndirs) {
+template <typename P>
+__global__ void k_cc_merge(P pred, unsigned int* __restrict__ parent, int D,
+                           int H, int W, int ndirs) {
     long long n = (long long)D * H * W;
     long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
     long long stride = gridDim.x * (long long)blockDim.x;
     for (; i < n; i += stride) {
-        if (!fg[i]) continue;
+        const auto vi = pred.v[i];
+        if (!P::fg(vi)) continue;
         int x = (int)(i % W);
         long long t = i / W;
         int y = (int)(t % H);
@@ -118,18 +144,19 @@ __global__ void k_cc_merge(const unsigned char* __restrict__ fg,
             int nx = x + BWD[d][2];
             if (nz < 0 || ny < 0 || ny >= H || nx < 0 || nx >= W) continue;
             long long j = ((long long)nz * H + ny) * W + nx;
-            if (fg[j]) cc_union(parent, (unsigned int)i, (unsigned int)j);
+            if (P::same(vi, pred.v[j]))
+                cc_union(parent, (unsigned int)i, (unsigned int)j);
         }
     }
 }
 
-__global__ void k_cc_compress(const unsigned char* __restrict__ fg,
-                              unsigned int* __restrict__ parent,
+template <typename P>
+__global__ void k_cc_compress(P pred, unsigned int* __restrict__ parent,
                               long long n) {
     long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
     long long stride = gridDim.x * (long long)blockDim.x;
     for (; i < n; i += stride)
-        if (fg[i])
+        if (P::fg(pred.v[i]))
             cc_st(parent, (unsigned int)i,
                   cc_find_ro(parent, (unsigned int)i));
 }
@@ -177,7 +204,8 @@ __global__ void k_cc_rank(const unsigned int* __restrict__ parent,
     }
 }
 
-__global__ void k_cc_final(const unsigned char* __restrict__ fg,
+template <typename P>
+__global__ void k_cc_final(P pred,
                            const unsigned int* __restrict__ parent,
                            const unsigned int* __restrict__ newlabel,
                            unsigned int* __restrict__ labels, long long n) {
@@ -185,7 +213,8 @@ __global__ void k_cc_final(const unsigned char* __restrict__ fg,
     long long stride = gridDim.x * (long long)blockDim.x;
     for (; i < n; i += stride)
         labels[i] =
-            fg[i] ? cc_ld(newlabel, cc_ld(parent, (unsigned int)i)) : 0u;
+            P::fg(pred.v[i])
+                ? cc_ld(newlabel, cc_ld(parent, (unsigned int)i)) : 0u;
 }
 
 __global__ void k_threshold(const float* __restrict__ in,
@@ -206,6 +235,75 @@ __global__ void k_nonzero_u8(const unsigned char* __restrict__ in,
 inline int grid_for(long long work, int threads) {
     long long want = (work + threads - 1) / threads;
     return (int)(want < 8192 ? want : 8192);
+}
+
+// init / merge / compress / count / rank / final over one predicate;
+// elem_bytes is sizeof(P's voxel type), for the profile's byte count only
+template <typename P>
+int run_cc(cfx_ctx* ctx, P pred, int elem_bytes, const int dims[3],
+           int connectivity, unsigned int* labels, unsigned int* scratch,
+           long long* n_components) {
+    int D = dims[0], H = dims[1], W = dims[2];
+    if (D <= 0 || H <= 0 || W <= 0) {
+        g_err = "connected_components: empty volume";
+        return -1;
+    }
+    long long n = (long long)D * H * W;
+    if (n >= 0xFFFFFFFFll) {
+        g_err = "connected_components: volume exceeds u32 indexing";
+        return -1;
+    }
+    int ndirs = connectivity == 6 ? 3 : connectivity == 18 ? 9
+                : connectivity == 26 ? 13 : -1;
+    if (ndirs < 0) {
+        g_err = "connectivity must be 6, 18 or 26";
+        return -1;
+    }
+    hipEvent_t e0;
+    if (prof_begin(ctx, &e0)) return -1;
+    hipLaunchKernelGGL(k_cc_init<P>, dim3(grid_for(n, 256)), dim3(256), 0,
+                       ctx->stream, pred, labels, n);
+    hipLaunchKernelGGL(k_cc_merge<P>, dim3(grid_for(n, 256)), dim3(256), 0,
+                       ctx->stream, pred, labels, D, H, W, ndirs);
+    hipLaunchKernelGGL(k_cc_compress<P>, dim3(grid_for(n, 256)), dim3(256),
+                       0, ctx->stream, pred, labels, n);
+
+    int nchunks = (int)((n + SCAN_CHUNK - 1) / SCAN_CHUNK);
+    if (ctx->cc_counts_cap < nchunks) {
+        if (ctx->cc_counts) (void)hipFree(ctx->cc_counts);
+        ctx->cc_counts = nullptr;
+        ctx->cc_counts_cap = 0;
+        CFX_CHECK(hipMalloc(&ctx->cc_counts,
+                            (size_t)nchunks * sizeof(unsigned int)));
+        ctx->cc_counts_cap = nchunks;
+    }
+    hipLaunchKernelGGL(k_cc_count, dim3(nchunks), dim3(64), 0, ctx->stream,
+                       labels, n, ctx->cc_counts);
+    // exclusive scan of the (small) per-chunk counts on the host
+    std::vector<unsigned int> counts(nchunks);
+    CFX_CHECK(hipMemcpyAsync(counts.data(), ctx->cc_counts,
+                             (size_t)nchunks * sizeof(unsigned int),
+                             hipMemcpyDeviceToHost, ctx->stream));
+    CFX_CHECK(hipStreamSynchronize(ctx->stream));
+    unsigned long long total = 0;
+    for (int i = 0; i < nchunks; ++i) {
+        unsigned int c = counts[i];
+        counts[i] = (unsigned int)total;
+        total += c;
+    }
+    *n_components = (long long)total;
+    CFX_CHECK(hipMemcpyAsync(ctx->cc_counts, counts.data(),
+                             (size_t)nchunks * sizeof(unsigned int),
+                             hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_cc_rank, dim3(nchunks), dim3(64), 0, ctx->stream,
+                       labels, n, ctx->cc_counts, scratch);
+    hipLaunchKernelGGL(k_cc_final<P>, dim3(grid_for(n, 256)), dim3(256), 0,
+                       ctx->stream, pred, labels, scratch, labels, n);
+    CFX_CHECK(hipGetLastError());
+    // algorithmic bytes: voxel reads x3 + parent RMW passes + final gather
+    double bytes = (double)n * (3.0 * elem_bytes + 4.0 * 6.0);
+    if (prof_end(ctx, e0, CFX_K_CC, bytes)) return -1;
+    return 0;
 }
 
 }  // namespace
@@ -236,59 +334,31 @@ extern "C" int cfx_connected_components(cfx_ctx* ctx,
                                         unsigned int* labels,
                                         unsigned int* scratch,
                                         long long* n_components) {
-    int D = dims[0], H = dims[1], W = dims[2];
-    long long n = (long long)D * H * W;
-    if (n >= 0xFFFFFFFFll) {
-        g_err = "connected_components: volume exceeds u32 indexing";
-        return -1;
-    }
-    int ndirs = connectivity == 6 ? 3 : connectivity == 18 ? 9
-                : connectivity == 26 ? 13 : -1;
-    if (ndirs < 0) {
-        g_err = "connectivity must be 6, 18 or 26";
-        return -1;
-    }
-    hipEvent_t e0;
-    if (prof_begin(ctx, &e0)) return -1;
-    hipLaunchKernelGGL(k_cc_init, dim3(grid_for(n, 256)), dim3(256), 0,
-                       ctx->stream, fg, labels, n);
-    hipLaunchKernelGGL(k_cc_merge, dim3(grid_for(n, 256)), dim3(256), 0,
-                       ctx->stream, fg, labels, D, H, W, ndirs);
-    hipLaunchKernelGGL(k_cc_compress, dim3(grid_for(n, 256)), dim3(256), 0,
-                       ctx->stream, fg, labels, n);
+    return run_cc(ctx, BinaryFg{fg}, 1, dims, connectivity, labels, scratch,
+                  n_components);
+}
 
-    int nchunks = (int)((n + SCAN_CHUNK - 1) / SCAN_CHUNK);
-    if (ctx->cc_counts_cap < nchunks) {
-        if (ctx->cc_counts) hipFree(ctx->cc_counts);
-        CFX_CHECK(hipMalloc(&ctx->cc_counts,
-                            (size_t)nchunks * sizeof(unsigned int)));
-        ctx->cc_counts_cap = nchunks;
-    }
-    hipLaunchKernelGGL(k_cc_count, dim3(nchunks), dim3(64), 0, ctx->stream,
-                       labels, n, ctx->cc_counts);
-    // exclusive scan of the (small) per-chunk counts on the host
-    std::vector<unsigned int> counts(nchunks);
-    CFX_CHECK(hipMemcpyAsync(counts.data(), ctx->cc_counts,
-                             (size_t)nchunks * sizeof(unsigned int),
-                             hipMemcpyDeviceToHost, ctx->stream));
-    CFX_CHECK(hipStreamSynchronize(ctx->stream));
-    unsigned long long total = 0;
-    for (int i = 0; i < nchunks; ++i) {
-        unsigned int c = counts[i];
-        counts[i] = (unsigned int)total;
-        total += c;
-    }
-    *n_components = (long long)total;
-    CFX_CHECK(hipMemcpyAsync(ctx->cc_counts, counts.data(),
-                             (size_t)nchunks * sizeof(unsigned int),
-                             hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_cc_rank, dim3(nchunks), dim3(64), 0, ctx->stream,
-                       labels, n, ctx->cc_counts, scratch);
-    hipLaunchKernelGGL(k_cc_final, dim3(grid_for(n, 256)), dim3(256), 0,
-                       ctx->stream, fg, labels, scratch, labels, n);
-    CFX_CHECK(hipGetLastError());
-    // algorithmic bytes: fg reads x3 + parent RMW passes + final gather
-    double bytes = (double)n * (3.0 * 1.0 + 4.0 * 6.0);
-    if (prof_end(ctx, e0, CFX_K_CC, bytes)) return -1;
-    return 0;
+/* seg: device label volume of 1-, 4- or 8-byte elements; one component per
+ * connected region of equal non-zero value. Buffers as above. */
+extern "C" int cfx_connected_components_labels(
+    cfx_ctx* ctx, const void* seg, int elem_bytes, const int dims[3],
+    int connectivity, unsigned int* labels, unsigned int* scratch,
+    long long* n_components) {
+    if (elem_bytes == 1)
+        return run_cc(
+            ctx, EqualValue<unsigned char>{
+                     static_cast<const unsigned char*>(seg)},
+            1, dims, connectivity, labels, scratch, n_components);
+    if (elem_bytes == 4)
+        return run_cc(
+            ctx, EqualValue<unsigned int>{
+                     static_cast<const unsigned int*>(seg)},
+            4, dims, connectivity, labels, scratch, n_components);
+    if (elem_bytes == 8)
+        return run_cc(
+            ctx, EqualValue<unsigned long long>{
+                     static_cast<const unsigned long long*>(seg)},
+            8, dims, connectivity, labels, scratch, n_components);
+    g_err = "connected_components_labels: elem_bytes must be 1, 4 or 8";
+    return -1;
 }

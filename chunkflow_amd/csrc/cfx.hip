@@ -59,6 +59,7 @@ extern "C" void cfx_destroy(cfx_ctx* ctx) {
     }
     if (ctx->dev_max) hipFree(ctx->dev_max);
     if (ctx->cc_counts) hipFree(ctx->cc_counts);
+    if (ctx->label_words) hipFree(ctx->label_words);
     delete ctx;
 }
 

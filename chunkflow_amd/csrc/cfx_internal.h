@@ -1,5 +1,5 @@
-// Shared internals of the chunkflow_amd extension (cfx.hip + cc.hip are
-// compiled into one shared object).
+// Shared internals of the chunkflow_amd extension (every csrc/*.hip
+// is compiled into one shared object).
 #ifndef CFX_INTERNAL_H
 #define CFX_INTERNAL_H
 
@@ -27,6 +27,8 @@ struct cfx_ctx {
     unsigned int* dev_max = nullptr;   // scratch for cfx_max
     unsigned int* cc_counts = nullptr;  // per-chunk root counts (cc.hip)
     int cc_counts_cap = 0;
+    // run-start total + status flags (labels.hip)
+    unsigned long long* label_words = nullptr;
 };
 
 extern thread_local std::string g_err;

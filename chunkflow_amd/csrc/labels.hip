@@ -1,0 +1,632 @@
+// Per-label voxel counts and label masking on gfx950: the device primitives
+// under chunkflow_amd/segmentation.py (unique_counts, mask_fragments,
+// mask_except — the reference's mask-out-objects operator, flow/flow.py
+// :2015-2050 + chunk/segmentation.py:86-109).
+//
+// Label table: open addressing with linear probing in caller-owned HBM.
+//   keys  u64[capacity]  32-bit labels are zero-extended; all-ones = empty,
+//                        so the label 2^64-1 is out of contract (the count
+//                        and insert kernels flag it as an error)
+//   vals  u32[capacity]  a voxel count, or a keep flag for mask_except
+// capacity is a power of two. The slot of a key is a 64-bit mix of ALL its
+// bits masked to the capacity, so label sets that agree in their low bits
+// (multiples of the capacity, ids differing only above bit 32) still spread.
+// Keys are only ever claimed (empty -> key, by CAS), never released, so a
+// probe sequence that meets its key or an empty slot is final. Every probe
+// loop runs at most `capacity` steps: on a table that is too small the
+// kernel raises a status flag and moves on, and the entry point returns an
+// error after the launch instead of spinning.
+//
+// The label stream is walked in flat (z,y,x) order. One lane owns SEG_BYTES
+// contiguous bytes (16 u32 / 8 u64 labels, four 16-byte loads) and keeps a
+// running (label, length): the table sees one insert + one atomicAdd (count
+// pass) or one lookup (apply pass) per RUN of equal labels in the segment,
+// not per voxel. A wave whose 64 segments all hold one and the same label —
+// background, the inside of a large object — combines them into a single
+// add, and a workgroup collects its runs in a small LDS table that it
+// flushes to HBM once at its end. Integer adds commute, so counts are exact
+// whatever the order.
+//
+// Alignment: the vector body starts at the first 16-byte-aligned element;
+// the elements before it and the partial segment after the last whole one
+// go through the scalar kernel (same code, element loads). An input and
+// output whose addresses differ modulo 16 take the scalar kernel throughout,
+// as the downsample kernels do for a misaligned start.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+
+#include "cfx_internal.h"
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int SEG_BYTES = 64;  // per lane: half a 128-byte line
+constexpr unsigned long long EMPTY = ~0ull;
+constexpr int kCountGrid = 2048;  // 8 workgroups per CU on 256 CUs
+
+enum : unsigned int { ST_FULL = 1u, ST_RESERVED = 2u };
+
+inline int grid_for(long long items) {
+    long long want = (items + kBlock - 1) / kBlock;
+    if (want < 1) want = 1;
+    return (int)(want < 16384 ? want : 16384);
+}
+
+// murmur3's 64-bit finalizer: every input bit reaches every output bit
+__device__ inline unsigned long long mix64(unsigned long long k) {
+    k ^= k >> 33;
+    k *= 0xff51afd7ed558ccdull;
+    k ^= k >> 33;
+    k *= 0xc4ceb9fe1a85ec53ull;
+    k ^= k >> 33;
+    return k;
+}
+
+struct Table {
+    unsigned long long* keys;
+    unsigned int* vals;
+    unsigned long long mask;  // capacity - 1
+};
+
+// slot of `key`, claiming an empty one if needed; -1 (and ST_FULL raised)
+// after `capacity` probes without success. Keys are read and claimed with
+// agent-scope atomics: the claiming CAS of another CU must be seen.
+__device__ inline long long table_insert(const Table& t,
+                                         unsigned long long key,
+                                         unsigned int* status) {
+    unsigned long long slot = mix64(key) & t.mask;
+    for (unsigned long long probe = 0; probe <= t.mask; ++probe) {
+        unsigned long long k = __hip_atomic_load(
+            &t.keys[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (k == EMPTY) k = atomicCAS(&t.keys[slot], EMPTY, key);
+        if (k == EMPTY || k == key) return (long long)slot;
+        slot = (slot + 1) & t.mask;
+    }
+    atomicOr(status, ST_FULL);
+    return -1;
+}
+
+// slot of `key` in a table no kernel is writing, or -1 if absent
+__device__ inline long long table_find(const Table& t,
+                                       unsigned long long key) {
+    unsigned long long slot = mix64(key) & t.mask;
+    for (unsigned long long probe = 0; probe <= t.mask; ++probe) {
+        unsigned long long k = t.keys[slot];
+        if (k == key) return (long long)slot;
+        if (k == EMPTY) return -1;
+        slot = (slot + 1) & t.mask;
+    }
+    return -1;
+}
+
+template <typename T, int N>
+union Vec {
+    uint4 q;
+    T e[N];
+};
+
+// Walk the lane's segment p[0..len) and call f(value, position, e) per
+// element, in order; e is the element's compile-time index within its
+// 16-byte vector (0 on the scalar path). VEC: len == SEG and p is 16-byte
+// aligned.
+template <typename T, bool VEC, typename F>
+__device__ inline void walk_segment(const T* __restrict__ p, int len, F&& f) {
+    constexpr int E = 16 / (int)sizeof(T);
+    constexpr int SEG = SEG_BYTES / (int)sizeof(T);
+    if (VEC) {
+#pragma unroll 1
+        for (int c = 0; c < SEG / E; ++c) {
+            Vec<T, E> v;
+            v.q = *reinterpret_cast<const uint4*>(p + c * E);
+#pragma unroll
+            for (int e = 0; e < E; ++e) f(v.e[e], c * E + e, e);
+        }
+    } else {
+#pragma unroll 1
+        for (int j = 0; j < len; ++j) f(p[j], j, 0);
+    }
+}
+
+// ---------------------------------------------------------------------------
+// table maintenance
+// ---------------------------------------------------------------------------
+__global__ void k_table_clear(unsigned long long* __restrict__ keys,
+                              unsigned int* __restrict__ vals,
+                              long long capacity) {
+    long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+         i < capacity; i += stride) {
+        keys[i] = EMPTY;
+        vals[i] = 0u;
+    }
+}
+
+__global__ void k_table_insert(Table t, const unsigned long long* ids,
+                               long long n_ids, unsigned int value,
+                               unsigned int* status) {
+    long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+         i < n_ids; i += stride) {
+        unsigned long long key = ids[i];
+        if (key == EMPTY) {
+            atomicOr(status, ST_RESERVED);
+            continue;
+        }
+        long long slot = table_insert(t, key, status);
+        // every writer of a slot stores the same value
+        if (slot >= 0)
+            __hip_atomic_store(&t.vals[slot], value, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// ---------------------------------------------------------------------------
+// run starts: voxels that differ from their flat predecessor, plus voxel 0
+// ---------------------------------------------------------------------------
+template <typename T, bool VEC>
+__global__ void k_run_starts(const T* __restrict__ in, long long begin,
+                             long long end,
+                             unsigned long long* __restrict__ total) {
+    constexpr int SEG = SEG_BYTES / (int)sizeof(T);
+    const long long n_items = (end - begin + SEG - 1) / SEG;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    unsigned int starts = 0;
+    for (long long item = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+         item < n_items; item += stride) {
+        long long s = begin + item * SEG;
+        int len = (int)(end - s < SEG ? end - s : SEG);
+        bool have_prev = s > 0;
+        T prev = have_prev ? in[s - 1] : T(0);
+        walk_segment<T, VEC>(in + s, len, [&](T v, int, int) {
+            starts += (!have_prev || v != prev) ? 1u : 0u;
+            have_prev = true;
+            prev = v;
+        });
+    }
+    for (int off = 32; off > 0; off >>= 1)
+        starts += __shfl_down(starts, off, 64);
+    if ((threadIdx.x & 63) == 0 && starts) atomicAdd(total, (unsigned long long)starts);
+}
+
+// ---------------------------------------------------------------------------
+// count pass
+// ---------------------------------------------------------------------------
+__device__ inline void count_run(const Table& t, unsigned long long key,
+                                 unsigned int len, unsigned int* status) {
+    if (key == EMPTY) {
+        atomicOr(status, ST_RESERVED);
+        return;
+    }
+    long long slot = table_insert(t, key, status);
+    if (slot >= 0) atomicAdd(&t.vals[slot], len);
+}
+
+// A small table of the same kind in LDS collects a workgroup's runs first:
+// a volume with few labels (background, large objects) would otherwise send
+// every run's add to the same few HBM words. A key that finds no LDS slot
+// within LDS_PROBES steps goes straight to the HBM table, so a workgroup
+// that meets more labels than the LDS table holds loses nothing.
+constexpr int LDS_SLOTS = 512;
+constexpr int LDS_PROBES = 4;
+
+__device__ inline void count_run_lds(unsigned long long* lkeys,
+                                     unsigned int* lvals, const Table& t,
+                                     unsigned long long key,
+                                     unsigned int len,
+                                     unsigned int* status) {
+    if (key == EMPTY) {
+        atomicOr(status, ST_RESERVED);
+        return;
+    }
+    unsigned int slot = (unsigned int)(mix64(key) >> 40) & (LDS_SLOTS - 1);
+    for (int probe = 0; probe < LDS_PROBES; ++probe) {
+        unsigned long long k = __hip_atomic_load(
+            &lkeys[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (k == EMPTY) k = atomicCAS(&lkeys[slot], EMPTY, key);
+        if (k == EMPTY || k == key) {
+            atomicAdd(&lvals[slot], len);
+            return;
+        }
+        slot = (slot + 1) & (LDS_SLOTS - 1);
+    }
+    count_run(t, key, len, status);
+}
+
+// blockDim is a multiple of 64 and the loop bound depends on the wave's
+// first item only, so all 64 lanes of a wave make the same number of trips
+// and the cross-lane operations below are convergent
+template <typename T, bool VEC>
+__global__ void k_count(const T* __restrict__ in, long long begin,
+                        long long end, Table t, unsigned int* status) {
+    constexpr int SEG = SEG_BYTES / (int)sizeof(T);
+    __shared__ unsigned long long lkeys[LDS_SLOTS];
+    __shared__ unsigned int lvals[LDS_SLOTS];
+    for (int i = threadIdx.x; i < LDS_SLOTS; i += blockDim.x) {
+        lkeys[i] = EMPTY;
+        lvals[i] = 0u;
+    }
+    __syncthreads();
+    const long long n_items = (end - begin + SEG - 1) / SEG;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    const int lane = threadIdx.x & 63;
+    for (long long item0 = (long long)blockIdx.x * blockDim.x
+                           + (threadIdx.x - lane);
+         item0 < n_items; item0 += stride) {
+        const long long item = item0 + lane;
+        const bool active = item < n_items;
+        T cur = T(0);
+        unsigned int runlen = 0, flushed = 0;
+        if (active) {
+            long long s = begin + item * SEG;
+            int len = (int)(end - s < SEG ? end - s : SEG);
+            walk_segment<T, VEC>(in + s, len, [&](T v, int, int) {
+                if (runlen != 0 && v != cur) {
+                    count_run_lds(lkeys, lvals, t, (unsigned long long)cur,
+                                  runlen, status);
+                    ++flushed;
+                    runlen = 0;
+                }
+                cur = v;
+                ++runlen;
+            });
+        }
+        // a wave whose 64 segments hold one label adds once; lane 0 of a
+        // wave with any active lane is active (items ascend)
+        const T first = __shfl(cur, 0, 64);
+        const bool uniform =
+            __all(!active || (flushed == 0 && cur == first));
+        if (uniform) {
+            unsigned int sum = active ? runlen : 0u;
+            for (int off = 32; off > 0; off >>= 1)
+                sum += __shfl_down(sum, off, 64);
+            if (lane == 0 && active)
+                count_run_lds(lkeys, lvals, t, (unsigned long long)cur, sum,
+                              status);
+        } else if (active) {
+            count_run_lds(lkeys, lvals, t, (unsigned long long)cur, runlen,
+                          status);
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < LDS_SLOTS; i += blockDim.x)
+        if (lkeys[i] != EMPTY) count_run(t, lkeys[i], lvals[i], status);
+}
+
+// ---------------------------------------------------------------------------
+// apply pass: out = keep(label) ? label : 0, one lookup per run
+//   MODE 0 (fragments): keep iff the label's count exceeds `threshold`
+//   MODE 1 (except):    keep iff the label is in the table with a set flag
+// Zero is written as zero without a lookup.
+// ---------------------------------------------------------------------------
+template <int MODE>
+__device__ inline bool keep_label(const Table& t, unsigned long long key,
+                                  long long threshold) {
+    long long slot = table_find(t, key);
+    if (slot < 0) return false;
+    unsigned int val = t.vals[slot];
+    return MODE == 0 ? (long long)val > threshold : val != 0u;
+}
+
+template <typename T, bool VEC, int MODE>
+__global__ void k_apply(const T* __restrict__ in, T* __restrict__ out,
+                        long long begin, long long end, Table t,
+                        long long threshold) {
+    constexpr int E = 16 / (int)sizeof(T);
+    constexpr int SEG = SEG_BYTES / (int)sizeof(T);
+    const long long n_items = (end - begin + SEG - 1) / SEG;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long item = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+         item < n_items; item += stride) {
+        long long s = begin + item * SEG;
+        int len = (int)(end - s < SEG ? end - s : SEG);
+        T cur = T(0);       // zero is never kept: the right initial state
+        bool keep = false;
+        Vec<T, E> o;
+        walk_segment<T, VEC>(in + s, len, [&](T v, int j, int e) {
+            if (v != cur) {
+                cur = v;
+                keep = v != T(0)
+                       && keep_label<MODE>(t, (unsigned long long)v,
+                                           threshold);
+            }
+            T r = keep ? v : T(0);
+            if (VEC) {
+                o.e[e] = r;
+                if (e == E - 1)
+                    *reinterpret_cast<uint4*>(out + s + (j - (E - 1))) = o.q;
+            } else {
+                out[s + j] = r;
+            }
+        });
+    }
+}
+
+// ---------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------
+inline unsigned int misalign16(const void* p) {
+    return (unsigned int)(reinterpret_cast<uintptr_t>(p) & 15);
+}
+
+// [0, head) scalar, [head, head + body) vector, [head + body, n) scalar;
+// `same_phase` is false when a second stream (the output) does not share
+// the input's address modulo 16 — then everything is scalar
+template <typename T>
+void split_range(const T* in, long long n, bool same_phase, long long* head,
+                 long long* body) {
+    constexpr int SEG = SEG_BYTES / (int)sizeof(T);
+    unsigned int mis = misalign16(in);
+    if (!same_phase || mis % sizeof(T) != 0) {
+        *head = n;
+        *body = 0;
+        return;
+    }
+    long long h = mis ? (16 - mis) / (long long)sizeof(T) : 0;
+    if (h > n) h = n;
+    *head = h;
+    *body = (n - h) / SEG * SEG;
+}
+
+int check_table(const void* keys, const void* vals, long long capacity,
+                const char* who) {
+    if (!keys || !vals) {
+        g_err = std::string(who) + ": null table";
+        return -1;
+    }
+    if (capacity < 1 || (capacity & (capacity - 1)) != 0) {
+        g_err = std::string(who) + ": table capacity must be a power of two";
+        return -1;
+    }
+    return 0;
+}
+
+int check_volume(const int dims[3], int elem_bytes, const char* who,
+                 long long* n) {
+    if (dims[0] <= 0 || dims[1] <= 0 || dims[2] <= 0) {
+        g_err = std::string(who) + ": empty input";
+        return -1;
+    }
+    if (elem_bytes != 4 && elem_bytes != 8) {
+        g_err = std::string(who) + ": elem_bytes must be 4 or 8";
+        return -1;
+    }
+    *n = (long long)dims[0] * dims[1] * dims[2];
+    if (*n > 0xFFFFFFFFll) {
+        g_err = std::string(who) + ": more voxels than a u32 count holds";
+        return -1;
+    }
+    return 0;
+}
+
+// two u64 words of context scratch: [0] run-start total, [1] status flags
+int status_words(cfx_ctx* ctx, unsigned long long** words) {
+    if (!ctx->label_words)
+        CFX_CHECK(hipMalloc(&ctx->label_words,
+                            2 * sizeof(unsigned long long)));
+    *words = ctx->label_words;
+    return 0;
+}
+
+int read_status(cfx_ctx* ctx, unsigned long long* word, const char* who) {
+    unsigned long long st = 0;
+    CFX_CHECK(hipMemcpyAsync(&st, word, sizeof(st), hipMemcpyDeviceToHost,
+                             ctx->stream));
+    CFX_CHECK(hipStreamSynchronize(ctx->stream));
+    if (st & ST_RESERVED) {
+        g_err = std::string(who)
+                + ": the label 2^64-1 is reserved (empty-slot key)";
+        return -1;
+    }
+    if (st & ST_FULL) {
+        g_err = std::string(who)
+                + ": label table full (more distinct labels than capacity)";
+        return -1;
+    }
+    return 0;
+}
+
+template <typename T>
+int launch_run_starts(cfx_ctx* ctx, const T* in, long long n,
+                      unsigned long long* total) {
+    constexpr int SEG = SEG_BYTES / (int)sizeof(T);
+    long long head, body;
+    split_range(in, n, true, &head, &body);
+    if (head > 0)
+        hipLaunchKernelGGL((k_run_starts<T, false>),
+                           dim3(std::min(grid_for((head + SEG - 1) / SEG),
+                                         kCountGrid)),
+                           dim3(kBlock), 0, ctx->stream, in, 0ll, head,
+                           total);
+    if (body > 0)
+        // one add per wave to a single word: keep the waves few
+        hipLaunchKernelGGL((k_run_starts<T, true>),
+                           dim3(std::min(grid_for(body / SEG), kCountGrid)),
+                           dim3(kBlock), 0,
+                           ctx->stream, in, head, head + body, total);
+    if (head + body < n)
+        hipLaunchKernelGGL((k_run_starts<T, false>), dim3(1), dim3(kBlock),
+                           0, ctx->stream, in, head + body, n, total);
+    CFX_CHECK(hipGetLastError());
+    return 0;
+}
+
+template <typename T>
+int launch_count(cfx_ctx* ctx, const T* in, long long n, Table t,
+                 unsigned int* status) {
+    constexpr int SEG = SEG_BYTES / (int)sizeof(T);
+    long long head, body;
+    split_range(in, n, true, &head, &body);
+    if (head > 0)
+        hipLaunchKernelGGL((k_count<T, false>),
+                           dim3(std::min(grid_for((head + SEG - 1) / SEG),
+                                         kCountGrid)),
+                           dim3(kBlock), 0, ctx->stream, in, 0ll, head, t,
+                           status);
+    if (body > 0)
+        // few, long-lived workgroups: each flushes its LDS table once
+        hipLaunchKernelGGL((k_count<T, true>),
+                           dim3(std::min(grid_for(body / SEG), kCountGrid)),
+                           dim3(kBlock), 0, ctx->stream, in, head,
+                           head + body, t, status);
+    if (head + body < n)
+        hipLaunchKernelGGL((k_count<T, false>), dim3(1), dim3(kBlock), 0,
+                           ctx->stream, in, head + body, n, t, status);
+    CFX_CHECK(hipGetLastError());
+    return 0;
+}
+
+template <typename T, int MODE>
+int launch_apply(cfx_ctx* ctx, const T* in, T* out, long long n, Table t,
+                 long long threshold) {
+    constexpr int SEG = SEG_BYTES / (int)sizeof(T);
+    long long head, body;
+    split_range(in, n, misalign16(in) == misalign16(out), &head, &body);
+    if (head > 0)
+        hipLaunchKernelGGL((k_apply<T, false, MODE>),
+                           dim3(grid_for((head + SEG - 1) / SEG)),
+                           dim3(kBlock), 0, ctx->stream, in, out, 0ll, head,
+                           t, threshold);
+    if (body > 0)
+        hipLaunchKernelGGL((k_apply<T, true, MODE>),
+                           dim3(grid_for(body / SEG)), dim3(kBlock), 0,
+                           ctx->stream, in, out, head, head + body, t,
+                           threshold);
+    if (head + body < n)
+        hipLaunchKernelGGL((k_apply<T, false, MODE>), dim3(1), dim3(kBlock),
+                           0, ctx->stream, in, out, head + body, n, t,
+                           threshold);
+    CFX_CHECK(hipGetLastError());
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int cfx_label_run_starts(cfx_ctx* ctx, const void* labels,
+                                    int elem_bytes, const int dims[3],
+                                    long long* n_runs) {
+    long long n;
+    if (check_volume(dims, elem_bytes, "label_run_starts", &n)) return -1;
+    unsigned long long* words;
+    if (status_words(ctx, &words)) return -1;
+    hipEvent_t e0;
+    if (prof_begin(ctx, &e0)) return -1;
+    CFX_CHECK(hipMemsetAsync(words, 0, sizeof(unsigned long long),
+                             ctx->stream));
+    int rc = elem_bytes == 4
+        ? launch_run_starts(ctx, static_cast<const unsigned int*>(labels),
+                            n, words)
+        : launch_run_starts(
+              ctx, static_cast<const unsigned long long*>(labels), n, words);
+    if (rc) return rc;
+    if (prof_end(ctx, e0, CFX_K_LABELS, (double)n * elem_bytes)) return -1;
+    unsigned long long total = 0;
+    CFX_CHECK(hipMemcpyAsync(&total, words, sizeof(total),
+                             hipMemcpyDeviceToHost, ctx->stream));
+    CFX_CHECK(hipStreamSynchronize(ctx->stream));
+    *n_runs = (long long)total;
+    return 0;
+}
+
+extern "C" int cfx_label_table_clear(cfx_ctx* ctx, unsigned long long* keys,
+                                     unsigned int* vals,
+                                     long long capacity) {
+    if (check_table(keys, vals, capacity, "label_table_clear")) return -1;
+    hipLaunchKernelGGL(k_table_clear, dim3(grid_for(capacity)), dim3(kBlock),
+                       0, ctx->stream, keys, vals, capacity);
+    CFX_CHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int cfx_label_table_insert(cfx_ctx* ctx,
+                                      const unsigned long long* ids,
+                                      long long n_ids, unsigned int value,
+                                      unsigned long long* keys,
+                                      unsigned int* vals,
+                                      long long capacity) {
+    if (check_table(keys, vals, capacity, "label_table_insert")) return -1;
+    if (n_ids < 0 || (n_ids > 0 && !ids)) {
+        g_err = "label_table_insert: bad id list";
+        return -1;
+    }
+    if (n_ids == 0) return 0;
+    unsigned long long* words;
+    if (status_words(ctx, &words)) return -1;
+    unsigned int* status = reinterpret_cast<unsigned int*>(words + 1);
+    CFX_CHECK(hipMemsetAsync(words + 1, 0, sizeof(unsigned long long),
+                             ctx->stream));
+    Table t{keys, vals, (unsigned long long)capacity - 1};
+    hipLaunchKernelGGL(k_table_insert, dim3(grid_for(n_ids)), dim3(kBlock),
+                       0, ctx->stream, t, ids, n_ids, value, status);
+    CFX_CHECK(hipGetLastError());
+    return read_status(ctx, words + 1, "label_table_insert");
+}
+
+extern "C" int cfx_label_count(cfx_ctx* ctx, const void* labels,
+                               int elem_bytes, const int dims[3],
+                               unsigned long long* keys, unsigned int* vals,
+                               long long capacity) {
+    long long n;
+    if (check_volume(dims, elem_bytes, "label_count", &n)) return -1;
+    if (check_table(keys, vals, capacity, "label_count")) return -1;
+    unsigned long long* words;
+    if (status_words(ctx, &words)) return -1;
+    unsigned int* status = reinterpret_cast<unsigned int*>(words + 1);
+    hipEvent_t e0;
+    if (prof_begin(ctx, &e0)) return -1;
+    CFX_CHECK(hipMemsetAsync(words + 1, 0, sizeof(unsigned long long),
+                             ctx->stream));
+    Table t{keys, vals, (unsigned long long)capacity - 1};
+    int rc = elem_bytes == 4
+        ? launch_count(ctx, static_cast<const unsigned int*>(labels), n, t,
+                       status)
+        : launch_count(ctx, static_cast<const unsigned long long*>(labels),
+                       n, t, status);
+    if (rc) return rc;
+    if (prof_end(ctx, e0, CFX_K_LABELS, (double)n * elem_bytes)) return -1;
+    return read_status(ctx, words + 1, "label_count");
+}
+
+extern "C" int cfx_label_mask(cfx_ctx* ctx, const void* in, void* out,
+                              int elem_bytes, const int dims[3],
+                              const unsigned long long* keys,
+                              const unsigned int* vals, long long capacity,
+                              int mode, long long threshold) {
+    long long n;
+    if (check_volume(dims, elem_bytes, "label_mask", &n)) return -1;
+    if (check_table(keys, vals, capacity, "label_mask")) return -1;
+    if (mode != 0 && mode != 1) {
+        g_err = "label_mask: mode must be 0 (count > threshold) or 1 (flag)";
+        return -1;
+    }
+    if (!in || !out) {
+        g_err = "label_mask: null volume";
+        return -1;
+    }
+    hipEvent_t e0;
+    if (prof_begin(ctx, &e0)) return -1;
+    Table t{const_cast<unsigned long long*>(keys),
+            const_cast<unsigned int*>(vals),
+            (unsigned long long)capacity - 1};
+    int rc;
+    if (elem_bytes == 4) {
+        auto* i4 = static_cast<const unsigned int*>(in);
+        auto* o4 = static_cast<unsigned int*>(out);
+        rc = mode == 0
+            ? launch_apply<unsigned int, 0>(ctx, i4, o4, n, t, threshold)
+            : launch_apply<unsigned int, 1>(ctx, i4, o4, n, t, threshold);
+    } else {
+        auto* i8 = static_cast<const unsigned long long*>(in);
+        auto* o8 = static_cast<unsigned long long*>(out);
+        rc = mode == 0
+            ? launch_apply<unsigned long long, 0>(ctx, i8, o8, n, t,
+                                                  threshold)
+            : launch_apply<unsigned long long, 1>(ctx, i8, o8, n, t,
+                                                  threshold);
+    }
+    if (rc) return rc;
+    if (prof_end(ctx, e0, CFX_K_LABELS, 2.0 * (double)n * elem_bytes))
+        return -1;
+    return 0;
+}

@@ -11,6 +11,8 @@ operators (reference chunkflow/flow/flow.py):
   crop-margin           :2053-2084
   plugin                :1751-1800
   connected-components  :1803-1829 (gfx950 union-find on device chunks)
+  mask-out-objects      :2015-2050 (dust removal + object selection; gfx950
+                                   label-table kernels on device chunks)
   normalize-contrast    :1672-1710 (device histogram/LUT kernels)
   load-h5 / save-h5     :976-1120  (in-repo HDF5 codec — h5io.py)
   load-tif / save-tif   :918-974   (in-repo TIFF codec — tiffio.py)
@@ -362,6 +364,37 @@ def connected_components(tasks, name, input_chunk_name, output_chunk_name,
                 task[input_chunk_name], threshold=threshold,
                 connectivity=connectivity)
             task['log']['timer'][name] = time() - start
+        yield task
+
+
+@main.command('mask-out-objects')
+@click.option('--input-chunk-name', '-i', type=str,
+              default=DEFAULT_CHUNK_NAME)
+@click.option('--output_chunk_name', '-o', type=str,
+              default=DEFAULT_CHUNK_NAME)
+@click.option('--dust-size-threshold', '-d', type=click.INT, default=None,
+              help='eliminate small objects with voxel number less than '
+                   'threshold.')
+@click.option('--selected-obj-ids', '-s', type=str, default=None,
+              help='a list of segment ids to keep, separated by comma '
+                   'without space, such as "34,56,78,90"; or a json file '
+                   'that contains a list of ids (a local path or file://).')
+@operator
+def mask_out_objects(tasks, input_chunk_name, output_chunk_name,
+                     dust_size_threshold, selected_obj_ids):
+    """Mask out objects in a segmentation chunk (device chunks stay on the
+    device)."""
+    from .segmentation import mask_out_objects as _mask_out_objects
+    from .segmentation import parse_obj_ids
+    selected_obj_ids = parse_obj_ids(selected_obj_ids)
+    if selected_obj_ids is not None:
+        print(f'number of selected objects: {len(selected_obj_ids)}')
+    for task in tasks:
+        if task is not None:
+            task[output_chunk_name] = _mask_out_objects(
+                task[input_chunk_name],
+                dust_size_threshold=dust_size_threshold,
+                selected_obj_ids=selected_obj_ids)
         yield task
 
 

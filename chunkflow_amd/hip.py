@@ -23,7 +23,10 @@ SYMBOLS = [
     'cfx_multiply_mask', 'cfx_multiply_mask_max', 'cfx_max',
     'cfx_crop_margin',
     'cfx_mask_using_last_channel', 'cfx_threshold', 'cfx_nonzero_u8',
-    'cfx_connected_components', 'cfx_hist_u8', 'cfx_lut_apply_u8',
+    'cfx_connected_components', 'cfx_connected_components_labels',
+    'cfx_label_run_starts', 'cfx_label_table_clear',
+    'cfx_label_table_insert', 'cfx_label_count', 'cfx_label_mask',
+    'cfx_hist_u8', 'cfx_lut_apply_u8',
     'cfx_downsample_avg_u8', 'cfx_downsample_avg_f32',
     'cfx_downsample_mode2', 'cfx_downsample_mode3',
     'cfx_conv3_ndhwc', 'cfx_conv3_ndhwc_w32',
@@ -37,7 +40,7 @@ SYMBOLS = [
 KERNEL_IDS = {
     'blend': 0, 'extract': 1, 'normalize': 2, 'cast': 3, 'reciprocal': 4,
     'maskmul': 5, 'crop': 6, 'max': 7, 'myelin': 8, 'cc': 9, 'conv': 10,
-    'conv_stream': 11,
+    'conv_stream': 11, 'labels': 12,
 }
 
 _lib = None
@@ -250,6 +253,57 @@ class CfxContext:
             ctypes.c_void_p(scratch_ptr), ctypes.byref(ncomp)),
             'cfx_connected_components')
         return ncomp.value
+
+    def connected_components_labels(self, seg_ptr, elem_bytes, dims,
+                                    connectivity, labels_ptr,
+                                    scratch_ptr) -> int:
+        ncomp = ctypes.c_longlong(0)
+        self._chk(self.lib.cfx_connected_components_labels(
+            ctypes.c_void_p(self.ctx), ctypes.c_void_p(seg_ptr),
+            ctypes.c_int(elem_bytes), _i3(dims), ctypes.c_int(connectivity),
+            ctypes.c_void_p(labels_ptr), ctypes.c_void_p(scratch_ptr),
+            ctypes.byref(ncomp)), 'cfx_connected_components_labels')
+        return ncomp.value
+
+    # --- label tables (per-label counts, masking) ----------------------------
+    def label_run_starts(self, labels_ptr, elem_bytes, dims) -> int:
+        runs = ctypes.c_longlong(0)
+        self._chk(self.lib.cfx_label_run_starts(
+            ctypes.c_void_p(self.ctx), ctypes.c_void_p(labels_ptr),
+            ctypes.c_int(elem_bytes), _i3(dims), ctypes.byref(runs)),
+            'cfx_label_run_starts')
+        return runs.value
+
+    def label_table_clear(self, keys_ptr, vals_ptr, capacity):
+        self._chk(self.lib.cfx_label_table_clear(
+            ctypes.c_void_p(self.ctx), ctypes.c_void_p(keys_ptr),
+            ctypes.c_void_p(vals_ptr), ctypes.c_longlong(capacity)),
+            'cfx_label_table_clear')
+
+    def label_table_insert(self, ids_ptr, n_ids, value, keys_ptr, vals_ptr,
+                           capacity):
+        self._chk(self.lib.cfx_label_table_insert(
+            ctypes.c_void_p(self.ctx), ctypes.c_void_p(ids_ptr),
+            ctypes.c_longlong(n_ids), ctypes.c_uint(value),
+            ctypes.c_void_p(keys_ptr), ctypes.c_void_p(vals_ptr),
+            ctypes.c_longlong(capacity)), 'cfx_label_table_insert')
+
+    def label_count(self, labels_ptr, elem_bytes, dims, keys_ptr, vals_ptr,
+                    capacity):
+        self._chk(self.lib.cfx_label_count(
+            ctypes.c_void_p(self.ctx), ctypes.c_void_p(labels_ptr),
+            ctypes.c_int(elem_bytes), _i3(dims), ctypes.c_void_p(keys_ptr),
+            ctypes.c_void_p(vals_ptr), ctypes.c_longlong(capacity)),
+            'cfx_label_count')
+
+    def label_mask(self, in_ptr, out_ptr, elem_bytes, dims, keys_ptr,
+                   vals_ptr, capacity, mode, threshold=0):
+        self._chk(self.lib.cfx_label_mask(
+            ctypes.c_void_p(self.ctx), ctypes.c_void_p(in_ptr),
+            ctypes.c_void_p(out_ptr), ctypes.c_int(elem_bytes), _i3(dims),
+            ctypes.c_void_p(keys_ptr), ctypes.c_void_p(vals_ptr),
+            ctypes.c_longlong(capacity), ctypes.c_int(mode),
+            ctypes.c_longlong(threshold)), 'cfx_label_mask')
 
     def conv3_ndhwc_bf16(self, in_ptr, wgt_ptr, bias_ptr, residual_ptr,
                          out_ptr, n, d, h, w, c, k, do_elu=False):

@@ -180,6 +180,93 @@ class HipOps:
                                       t.element_size(), dims)
         return out
 
+    # --- label tables: per-label voxel counts and masking -------------------
+    # (semantics: chunkflow_amd/segmentation.py; kernels: csrc/labels.hip)
+    LABEL_TABLE_MIN = 64
+
+    @staticmethod
+    def _check_labels(t: torch.Tensor, who: str) -> torch.Tensor:
+        if t.ndim != 3:
+            raise ValueError(f'{who}: 3-D only: {tuple(t.shape)}')
+        if t.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f'{who}: device labels must be int32 or int64 '
+                            f'(carrying uint32 / uint64), but got: {t.dtype}')
+        if t.numel() == 0:
+            raise ValueError(f'{who}: empty volume')
+        return t.contiguous()
+
+    def _new_label_table(self, distinct_bound: int, device):
+        """A cleared table with room for `distinct_bound` keys at a load
+        factor of at most one half."""
+        capacity = self.LABEL_TABLE_MIN
+        while capacity < 2 * distinct_bound:
+            capacity *= 2
+        keys = torch.empty(capacity, dtype=torch.int64, device=device)
+        vals = torch.empty(capacity, dtype=torch.int32, device=device)
+        self.cfx.label_table_clear(keys.data_ptr(), vals.data_ptr(),
+                                   capacity)
+        return keys, vals, capacity
+
+    def label_count_table(self, t: torch.Tensor):
+        """(keys, vals, capacity, bound): the voxel count of every label of
+        a contiguous int32/int64 volume, zero included.
+
+        Sizing. In flat (z,y,x) order call voxel i a run start if i == 0 or
+        label[i] != label[i-1]. Every distinct label has a first occurrence
+        f in that order; either f == 0, or label[f-1] is a different label
+        (it occurred earlier, and label[f] had not) — so f is a run start,
+        and distinct labels map one-to-one onto some of the run starts.
+        Hence #distinct <= #run starts <= n: the table is sized from the run
+        starts (one streaming read), which for a real segmentation is about
+        surface / x-extent per object rather than one slot per voxel, and
+        can never come out too small."""
+        dims, eb = tuple(t.shape), t.element_size()
+        bound = self.cfx.label_run_starts(t.data_ptr(), eb, dims)
+        keys, vals, capacity = self._new_label_table(bound, t.device)
+        self.cfx.label_count(t.data_ptr(), eb, dims, keys.data_ptr(),
+                             vals.data_ptr(), capacity)
+        return keys, vals, capacity, bound
+
+    def label_unique_counts(self, t: torch.Tensor):
+        """(ids, counts): ids in t's dtype ascending by UNSIGNED value,
+        counts int64 — np.unique(return_counts=True) on the uint view."""
+        t = self._check_labels(t, 'label_unique_counts')
+        keys, vals, _, _ = self.label_count_table(t)
+        used = keys != -1
+        ids, counts = keys[used], vals[used]
+        # the table is small: ordering it is torch plumbing. Flipping the
+        # sign bit turns signed order into unsigned order.
+        order = torch.argsort(torch.bitwise_xor(ids, -2 ** 63))
+        return (ids[order].to(t.dtype),
+                counts[order].to(torch.int64) & 0xFFFFFFFF)
+
+    def label_mask_fragments(self, t: torch.Tensor,
+                             voxel_num_threshold: int) -> torch.Tensor:
+        t = self._check_labels(t, 'label_mask_fragments')
+        keys, vals, capacity, _ = self.label_count_table(t)
+        out = torch.empty_like(t)
+        self.cfx.label_mask(t.data_ptr(), out.data_ptr(), t.element_size(),
+                            tuple(t.shape), keys.data_ptr(), vals.data_ptr(),
+                            capacity, 0, int(voxel_num_threshold))
+        return out
+
+    def label_mask_except(self, t: torch.Tensor, ids) -> torch.Tensor:
+        """ids: distinct Python ints within the unsigned range of the
+        carried dtype (segmentation.valid_ids)."""
+        t = self._check_labels(t, 'label_mask_except')
+        keys, vals, capacity = self._new_label_table(len(ids), t.device)
+        if len(ids):
+            ids_dev = torch.from_numpy(
+                np.array(ids, dtype=np.uint64).view(np.int64)).to(t.device)
+            self.cfx.label_table_insert(ids_dev.data_ptr(), len(ids), 1,
+                                        keys.data_ptr(), vals.data_ptr(),
+                                        capacity)
+        out = torch.empty_like(t)
+        self.cfx.label_mask(t.data_ptr(), out.data_ptr(), t.element_size(),
+                            tuple(t.shape), keys.data_ptr(), vals.data_ptr(),
+                            capacity, 1, 0)
+        return out
+
 
 class TorchOps:
     is_hip = False

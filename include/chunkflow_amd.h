@@ -119,6 +119,56 @@ int cfx_connected_components(cfx_ctx* ctx, const unsigned char* fg,
                              const int dims[3], int connectivity,
                              unsigned int* labels, unsigned int* scratch,
                              long long* n_components);
+/* The same union-find over a label volume (elem_bytes 1, 4 or 8): a voxel
+ * is foreground iff non-zero, and two neighbours are united iff their
+ * values are equal as raw bit patterns (cc3d's multi-label semantics), so
+ * touching regions of different value stay apart. Same numbering, limits
+ * and buffers as above; seg must not alias labels or scratch. On a binary
+ * volume the two entries agree. */
+int cfx_connected_components_labels(cfx_ctx* ctx, const void* seg,
+                                    int elem_bytes, const int dims[3],
+                                    int connectivity, unsigned int* labels,
+                                    unsigned int* scratch,
+                                    long long* n_components);
+
+/* ---- per-label voxel counts and label masking (mask-out-objects) -------- */
+/* A label table is two caller-owned device arrays: keys u64[capacity]
+ * (32-bit labels zero-extended; all-ones marks an empty slot, so the label
+ * 2^64-1 is out of contract and reported as an error) and vals
+ * u32[capacity] (a voxel count or a keep flag). capacity must be a power
+ * of two and at least the number of distinct keys inserted; size it from
+ * cfx_label_run_starts. A table that turns out too small makes the call
+ * return an error ("label table full"); it never hangs. Volumes are (D, H,
+ * W) of 4- or 8-byte labels compared as raw bit patterns, at most 2^32-1
+ * voxels. */
+/* number of voxels that differ from their flat (z,y,x-order) predecessor,
+ * plus one for voxel 0: an upper bound on the number of distinct labels.
+ * Synchronous. */
+int cfx_label_run_starts(cfx_ctx* ctx, const void* labels, int elem_bytes,
+                         const int dims[3], long long* n_runs);
+/* every slot empty, every value 0 */
+int cfx_label_table_clear(cfx_ctx* ctx, unsigned long long* keys,
+                          unsigned int* vals, long long capacity);
+/* vals[slot(id)] = value for each of n_ids device-resident u64 ids
+ * (duplicates allowed). Synchronous (reads the status flags back). */
+int cfx_label_table_insert(cfx_ctx* ctx, const unsigned long long* ids,
+                           long long n_ids, unsigned int value,
+                           unsigned long long* keys, unsigned int* vals,
+                           long long capacity);
+/* vals[slot(label)] += voxel count of that label, zero included, on a
+ * cleared table. Synchronous (reads the status flags back). */
+int cfx_label_count(cfx_ctx* ctx, const void* labels, int elem_bytes,
+                    const int dims[3], unsigned long long* keys,
+                    unsigned int* vals, long long capacity);
+/* out[i] = keep(in[i]) ? in[i] : 0, zero staying zero. mode 0: keep iff the
+ * label's value in the table is > threshold (dust removal over a counted
+ * table); mode 1: keep iff the label is in the table with a non-zero value
+ * (threshold unused). Labels absent from the table are zeroed. in == out is
+ * allowed. */
+int cfx_label_mask(cfx_ctx* ctx, const void* in, void* out, int elem_bytes,
+                   const int dims[3], const unsigned long long* keys,
+                   const unsigned int* vals, long long capacity, int mode,
+                   long long threshold);
 
 /* ---- image normalization (normalize-contrast operator) ----------------- */
 /* zero + accumulate nsec 256-bin u32 histograms, one per contiguous
@@ -225,7 +275,8 @@ enum cfx_kernel_id {
     CFX_K_CC = 9,
     CFX_K_CONV = 10,
     CFX_K_CONV_STREAM = 11,  /* up/down-sample + (1,5,5) stream convs */
-    CFX_K_COUNT = 12
+    CFX_K_LABELS = 12,       /* label run-start / count / mask passes */
+    CFX_K_COUNT = 13
 };
 int cfx_profile_enable(cfx_ctx* ctx, int enable);
 int cfx_profile_reset(cfx_ctx* ctx);
