@@ -1,6 +1,6 @@
 """Exact-arithmetic inputs, f64 CPU references and comparisons for the
 hand-written conv kernels (used by tests/test_conv_exact.py and by the
-CFX_ZRING_PL variant sweep in tests/test_gpu_parity.py).
+bf16 C=28 ring test in tests/test_gpu_parity.py).
 
 The idea: feed the kernels small-integer data. Every product and every
 partial sum is then an integer far below 2^24, so f32 accumulation is exact

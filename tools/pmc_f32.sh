@@ -1,12 +1,13 @@
 #!/bin/bash
 # SQ stall decomposition of the f32 zring (same recipe as pmc_bf16.sh).
+set -o pipefail  # pmc= below reports the profiled run, not tail
 repo=$(pwd)
 cd /tmp && export TMPDIR=/tmp && cd "$repo"
 timeout 420 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY \
   SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_LDS \
   SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE \
   --output-format csv -d gpurun_out/pmc_f32 -- \
-  python tools/zring_ab.py > gpurun_out/pmc_f32.log 2>&1
+  python tools/conv_probe.py 2>&1 | tail -n 20  # the probe's result rows
 echo pmc=$?
 python - << 'PYEOF'
 import csv, glob, collections
