@@ -6,7 +6,7 @@
 // pinned bit-exactly by tests/test_conv_exact.py):
 //   cfx_conv3_ndhwc        k_conv3 slab, C = 28/36/48/64
 //   cfx_conv3_ndhwc_w32    k_conv3_w32 (32x32x2), C = 28
-//   cfx_conv3_ndhwc_zring  k_conv3_zring_pl, C = 28 [96.8 TF] and 36;
+//   cfx_conv3_ndhwc_zring  k_conv3_zring_pl, C = 28 [111 TF] and 36;
 //                          k_conv3_zring_dw, C = 48 (37 TF, slower than
 //                          the slab; kept as the only C=48 ring route)
 //   cfx_conv3_ndhwc_bf16   k_conv3_zring_bf16_a, C = 28 [610-646 TF];
@@ -459,13 +459,17 @@ namespace {
 // planes run while those loads are in flight, then the registers drain to
 // the ring slot and ONE barrier per z releases the last 9 taps: iteration
 // z's store targets the slot plane z-2 occupied, whose last readers (dzi=0
-// of iteration z-1) sit before iteration z-1's barrier.
+// of iteration z-1) sit before iteration z-1's barrier. Per z the order of
+// memory traffic is: plane loads | 18 taps | plane stores, barrier |
+// residual loads | 9 taps | outputs finished in registers | stores back to
+// back — no wait ever sees a pending store (DESIGN.md §10-r2 item 8 has
+// what the assembly looked like before and what each part was worth).
 template <int C, int K, int TY, int TX, int NTK>
 __global__ __launch_bounds__(512, 1) void k_conv3_zring_pl(
     const float* __restrict__ in, const float* __restrict__ wgt,
     const float* __restrict__ bias, const float* __restrict__ res,
     float* __restrict__ out, int N, int D, int H, int W, int do_elu,
-    int j0) {
+    int j0, int wvec) {
     constexpr int PC = padc(C);
     constexpr int SX = TX + 2;
     constexpr int SY = TY + 2;
@@ -476,10 +480,12 @@ __global__ __launch_bounds__(512, 1) void k_conv3_zring_pl(
     constexpr int M_TILES = (TY * XT) / NW;
     constexpr int C4N = C / 4;
     constexpr int LV = (SY * SX * C4N + 511) / 512;  // loads held per thread
+    constexpr int WV4 = 27 * NT * C * 4;             // wall size in float4
+    constexpr int WL = (WV4 + 511) / 512;            // wall float4 per thread
     static_assert((TY * XT) % NW == 0, "");
 
-    __shared__ float ring[3 * SY * SX * PC];
-    __shared__ float wall[27 * NT * C * 16];
+    __shared__ __attribute__((aligned(16))) float ring[3 * SY * SX * PC];
+    __shared__ __attribute__((aligned(16))) float wall[27 * NT * C * 16];
 
     const int n = blockIdx.z;
     const int y0 = blockIdx.y * TY;
@@ -488,14 +494,48 @@ __global__ __launch_bounds__(512, 1) void k_conv3_zring_pl(
     const int wave = tid >> 6;
     const int lane = tid & 63;
 
-    for (int idx = tid; idx < 27 * NT * C * 16; idx += 512) {
-        const int j = idx & 15;
-        const int c = (idx >> 4) % C;
-        const int nt = (idx >> 4) / C % NT;
-        const int tap = (idx >> 4) / C / NT;
-        const int jg = j0 + nt * 16 + j;
-        wall[idx] =
-            jg < K ? wgt[((long long)tap * C + c) * K + jg] : 0.f;
+    // Weight wall, staged once per workgroup. wvec (host-checked: wgt
+    // 16-byte aligned, K % 4 == 0, and j0 % 4 == 0 by construction): a
+    // float4 of a (tap, c) weight row is four consecutive j of one wall
+    // row and lies either wholly below K or wholly in the zero padding,
+    // so the wall goes through registers as ONE batch of float4 loads
+    // from clamped addresses with the zero-select deferred to the LDS
+    // store, like plane_load/plane_store. The scalar loop is the
+    // fallback for a misaligned weight tensor: one dword per dependent
+    // L2 round trip.
+    auto wall_load = [&](f32x4 (&wv)[WL], bool (&wk)[WL]) {
+#pragma unroll
+        for (int li = 0; li < WL; ++li) {
+            const int idx = min(tid + li * 512, WV4 - 1);
+            const int row = idx >> 2;
+            const int c = row % C;
+            const int nt = row / C % NT;
+            const int tap = row / C / NT;
+            const int jg = j0 + nt * 16 + (idx & 3) * 4;
+            wk[li] = jg < K;
+            wv[li] = *reinterpret_cast<const f32x4*>(
+                wgt + ((long long)tap * C + c) * K + (jg < K ? jg : 0));
+        }
+    };
+    auto wall_store = [&](const f32x4 (&wv)[WL], const bool (&wk)[WL]) {
+#pragma unroll
+        for (int li = 0; li < WL; ++li) {
+            const int idx = tid + li * 512;
+            if (idx >= WV4) break;
+            *reinterpret_cast<f32x4*>(&wall[idx * 4]) =
+                wk[li] ? wv[li] : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    };
+    if (!wvec) {
+        for (int idx = tid; idx < 27 * NT * C * 16; idx += 512) {
+            const int j = idx & 15;
+            const int c = (idx >> 4) % C;
+            const int nt = (idx >> 4) / C % NT;
+            const int tap = (idx >> 4) / C / NT;
+            const int jg = j0 + nt * 16 + j;
+            wall[idx] =
+                jg < K ? wgt[((long long)tap * C + c) * K + jg] : 0.f;
+        }
     }
 
     const bool xy_interior = y0 >= 1 && y0 + TY + 1 <= H && x0 >= 1 &&
@@ -503,13 +543,24 @@ __global__ __launch_bounds__(512, 1) void k_conv3_zring_pl(
 
     // Unconditional clamped loads + deferred zero-select (a select
     // attached to each load makes hipcc emit a full vmcnt(0) drain per
-    // load, serializing the HBM latency)
+    // load, serializing the HBM latency). The load and the store phase
+    // are both free of control flow: a thread past the end of the plane
+    // in the last round handles its previous round's element a second
+    // time (same value to the same LDS address). With a per-thread
+    // `break` in the store phase hipcc sinks each load into the
+    // conditional block of its store, next to a vmcnt(0) — the loads
+    // then fly over nothing.
+    static_assert(SY * SX * C4N > 512 && SY * SX * C4N > (LV - 1) * 512, "");
+    auto plane_idx = [&](int li) {
+        const int idx = tid + li * 512;
+        return idx < SY * SX * C4N ? idx : idx - 512;
+    };
     auto plane_load = [&](int P, f32x4 (&vals)[LV], bool (&keep)[LV]) {
         const bool zin = P >= 0 && P < D;
         const bool interior = zin && xy_interior;
 #pragma unroll
         for (int li = 0; li < LV; ++li) {
-            const int idx = min(tid + li * 512, SY * SX * C4N - 1);
+            const int idx = plane_idx(li);
             const int c4 = idx % C4N;
             const int v = idx / C4N;
             const int gy = y0 + v / SX - 1;
@@ -528,8 +579,7 @@ __global__ __launch_bounds__(512, 1) void k_conv3_zring_pl(
         const int slot = ((P + 1) % 3 + 3) % 3;
 #pragma unroll
         for (int li = 0; li < LV; ++li) {
-            const int idx = tid + li * 512;
-            if (idx >= SY * SX * C4N) break;
+            const int idx = plane_idx(li);
             const int c4 = idx % C4N;
             const int v = idx / C4N;
             *reinterpret_cast<f32x4*>(
@@ -539,10 +589,14 @@ __global__ __launch_bounds__(512, 1) void k_conv3_zring_pl(
     };
 
     {
+        f32x4 wv[WL];
+        bool wk[WL];
         f32x4 v0[LV], v1[LV];
         bool k0[LV], k1[LV];
+        if (wvec) wall_load(wv, wk);  // one batch with the two planes
         plane_load(-1, v0, k0);
         plane_load(0, v1, k1);
+        if (wvec) wall_store(wv, wk);
         plane_store(-1, v0, k0);
         plane_store(0, v1, k1);
     }
@@ -560,6 +614,13 @@ __global__ __launch_bounds__(512, 1) void k_conv3_zring_pl(
     const int col16 = lane & 15;
     const int colj = lane & 15;
     const int rbase = (lane >> 4) * 4;
+
+    // the lane's bias values never change over z: loaded once (clamped
+    // address; lanes with j >= K store nothing)
+    float bj[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+        bj[t] = bias ? bias[min(j0 + t * 16 + colj, K - 1)] : 0.f;
 
     for (int z = 0; z < D; ++z) {
         // Two accumulator chains per m-tile: consecutive MFMAs on the
@@ -619,16 +680,27 @@ __global__ __launch_bounds__(512, 1) void k_conv3_zring_pl(
 
         f32x4 vals[LV];
         bool keep[LV];
+        // The sched_barriers pin the pipeline: without the first the
+        // scheduler sinks the loads down to the store phase, without the
+        // second it lifts the stores' zero-select (and its vmcnt(0)) up
+        // to the loads.
         plane_load(z + 1, vals, keep);  // flies over the next 18 taps
+        __builtin_amdgcn_sched_barrier(0);
         compute_dzi(0);
         compute_dzi(1);
+        __builtin_amdgcn_sched_barrier(0);
         plane_store(z + 1, vals, keep);
         __syncthreads();
-        compute_dzi(2);
 
+        // Residual reads, batched from clamped addresses and issued
+        // BEFORE the last 9 taps so they land under those MFMAs. Nothing
+        // else is in flight here: plane_store above waited for this z's
+        // plane loads, and with them for every older store. (A load in
+        // the store loop costs a vmcnt(0) drain each — loads and stores
+        // share the counter, so a wait behind a pending store is also a
+        // wait for that store's acknowledgement.)
         float rv[M_TILES][NT][4];
-        if (res) {  // residual reads batched from clamped addresses (a
-                    // load in the store loop costs a vmcnt(0) drain each)
+        if (res) {
 #pragma unroll
             for (int m = 0; m < M_TILES; ++m) {
                 const int gym = min(y0 + tmy[m], H - 1);
@@ -645,6 +717,30 @@ __global__ __launch_bounds__(512, 1) void k_conv3_zring_pl(
                 }
             }
         }
+        compute_dzi(2);
+
+        // Every output of this z is finished in registers first, so the
+        // stores below go out back to back with no wait between them.
+        // ELU is branch-free: expm1f of the value where it is not
+        // positive (0 elsewhere; NaN stays NaN), then a select.
+        float ov[M_TILES][NT][4];
+#pragma unroll
+        for (int m = 0; m < M_TILES; ++m) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    float v = acc[m][t][r] + bj[t];
+                    if (NT == 1) v += acc2[m][r];
+                    if (res) v += rv[m][t][r];
+                    if (do_elu) {
+                        const float e = expm1f(v > 0.f ? 0.f : v);
+                        v = v > 0.f ? v : e;
+                    }
+                    ov[m][t][r] = v;
+                }
+            }
+        }
 #pragma unroll
         for (int m = 0; m < M_TILES; ++m) {
             const int gy = y0 + tmy[m];
@@ -653,19 +749,12 @@ __global__ __launch_bounds__(512, 1) void k_conv3_zring_pl(
             for (int t = 0; t < NT; ++t) {
                 const int j = j0 + t * 16 + colj;
                 if (j >= K) continue;
-                const float bj = bias ? bias[j] : 0.f;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int gx = x0 + tmx[m] + rbase + r;
                     if (gx >= W) continue;
-                    long long o =
-                        ((((long long)n * D + z) * H + gy) * W + gx) * K +
-                        j;
-                    float v = acc[m][t][r] + bj;
-                    if (NT == 1) v += acc2[m][r];
-                    if (res) v += rv[m][t][r];
-                    if (do_elu) v = v > 0.f ? v : expm1f(v);
-                    out[o] = v;
+                    out[((((long long)n * D + z) * H + gy) * W + gx) * K +
+                        j] = ov[m][t][r];
                 }
             }
         }
@@ -874,11 +963,15 @@ extern "C" int cfx_conv3_ndhwc_zring(cfx_ctx* ctx, const float* in,
     dim3 grid((W + 15) / 16, (H + 7) / 8, (unsigned)N);
     hipEvent_t e0;
     if (prof_begin(ctx, &e0)) return -1;
+    // float4 wall staging needs 16-byte-aligned weight rows; otherwise the
+    // ring takes its scalar staging loop
+    const int wvec =
+        (reinterpret_cast<uintptr_t>(wgt) % 16 == 0 && K % 4 == 0) ? 1 : 0;
     if (C == 28 && K == 28) {
         // wall holds both K tiles (96.8 KB + 60.5 KB ring)
         hipLaunchKernelGGL((k_conv3_zring_pl<28, 28, 8, 16, 2>), grid,
                            dim3(512), 0, ctx->stream, in, wgt, bias,
-                           residual, out, N, D, H, W, do_elu, 0);
+                           residual, out, N, D, H, W, do_elu, 0, wvec);
     } else if (C == 36 && K == 36) {
         // one 16-wide K tile per launch (wall 62.2 KB + ring 77.8 KB);
         // the input re-read costs ~3x HBM traffic of a 113 MB activation
@@ -886,7 +979,7 @@ extern "C" int cfx_conv3_ndhwc_zring(cfx_ctx* ctx, const float* in,
         for (int j0 = 0; j0 < 36; j0 += 16) {
             hipLaunchKernelGGL((k_conv3_zring_pl<36, 36, 8, 16, 1>), grid,
                                dim3(512), 0, ctx->stream, in, wgt, bias,
-                               residual, out, N, D, H, W, do_elu, j0);
+                               residual, out, N, D, H, W, do_elu, j0, wvec);
         }
     } else if (C == 48 && K == 48) {
         // double-buffered per-dzi weight wall (full wall no longer fits

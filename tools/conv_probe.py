@@ -54,6 +54,53 @@ def probe(C, D, H, W, N=12, iters=10, w32=False, zring=False):
            'mine_TF': flops / tm / 1e12, 'torch_TF': flops / tt / 1e12,
            'speedup': tt / tm}, flush=True)
 
+def probe_zring(C, D, H, W, N=12, fused=False, iters=20, tag=''):
+    """Time the f32 z-ring alone (drained queue, synchronized warm-up),
+    plain (bias only) or fused (bias + residual + ELU), and print one JSON
+    line. For an A/B, run this in one process per library build and
+    alternate the builds; `tag` names the build in the line."""
+    import json
+    torch.manual_seed(0)
+    x = torch.randn(N, C, D, H, W, device='cuda').contiguous(memory_format=cl)
+    wt = torch.randn(C, C, 3, 3, 3, device='cuda') * (1.0 / (27 * C) ** 0.5)
+    bias = torch.randn(C, device='cuda') * 0.1
+    wtap = wt.permute(2, 3, 4, 1, 0).reshape(27, C, C).contiguous()
+    res = torch.randn_like(x) if fused else None
+    out = torch.empty_like(x)
+    cfx = get_cfx(0)
+
+    def run():
+        cfx.conv3_ndhwc(x.data_ptr(), wtap.data_ptr(), bias.data_ptr(),
+                        res.data_ptr() if fused else None, out.data_ptr(),
+                        N, D, H, W, C, C, do_elu=fused, zring=True)
+
+    for _ in range(5):
+        run()
+    torch.cuda.synchronize()
+    passes = []
+    for _ in range(3):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(iters):
+            run()
+        torch.cuda.synchronize()
+        passes.append((time.perf_counter() - t0) / iters * 1e3)
+    ms = min(passes)
+    flops = 2.0 * 27 * C * C * N * D * H * W
+    print(json.dumps({
+        'tag': tag, 'C': C, 'shape': [N, D, H, W], 'fused': fused,
+        'ms': round(ms, 4), 'ms_passes': [round(p, 4) for p in passes],
+        'TF': round(flops / ms / 1e9, 2),
+        'checksum': float(out.double().sum().item())}), flush=True)
+
+
+if __name__ == '__main__' and '--zring-stalls' in sys.argv:
+    _tag = sys.argv[sys.argv.index('--zring-stalls') + 1]
+    for _fused in (False, True):
+        probe_zring(28, 20, 256, 256, fused=_fused, tag=_tag)
+        probe_zring(36, 20, 128, 128, fused=_fused, tag=_tag)
+    sys.exit(0)
+
 if __name__ == '__main__' and '--bf16' not in sys.argv:
     probe(28, 20, 256, 256)
     probe(28, 20, 256, 256, w32=True)
