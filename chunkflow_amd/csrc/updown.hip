@@ -9,7 +9,9 @@
 // kernels are VALU streams: input row and weights staged to LDS in
 // batched coalesced loads (a per-load global read next to its use costs a
 // full vmcnt drain — the round-1 staging lesson), per-thread accumulators
-// over 8 x-positions so each weight vector is read once per c.
+// over 8 x-positions so each weight vector is read once per c. The f32
+// up-conv of MFMA-shaped widths and the 28 -> 3 output conv run on the f32
+// matrix cores instead (k_upconv2_mfma, k_conv155_out_mfma below).
 //
 // Layouts: NDHWC (channels_last_3d); weights packed
 // [parity q=(py<<1)|px][C][K] (stored in LDS as [c][k][q] float4 so one
@@ -17,6 +19,8 @@
 // No activation (RSUNet applies none here). f32 accumulation.
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
+
+#include <algorithm>
 
 #include "cfx_internal.h"
 
@@ -150,6 +154,195 @@ __global__ __launch_bounds__(256, 2) void k_upconv2(
             stf(op + (long long)2 * W * K, acc[p][2]);
             stf(op + (long long)2 * W * K + K, acc[p][3]);
         }
+    }
+}
+
+// ---- transposed conv (1,2,2) on the f32 MFMA, optional fused skip-add -----
+// out[n, z, 2y+py, 2x+px, k] = (bias[k] + sum_c in[n,z,y,x,c] * w[q][c][k])
+//                              (+ skip[n, z, 2y+py, 2x+px, k])
+// k_upconv2 above is LDS-bound (9 LDS reads per 32 FMAs), restages the
+// whole weight table for every 64 input positions and stores single
+// dwords. Here the op is the GEMM it is: per input position
+//   out4K[q*K + k] = sum_c in[c] * w[q][c][k]
+// with M = 16 input x positions (one tile), N = 4K = NT tiles of 16 and
+// C/4 steps of v_mfma_f32_16x16x4_f32 (f32 in, f32 accumulate, exact: an
+// fmaf chain over c in natural order that starts from the bias).
+//
+// One wave owns a tile; a workgroup of UM_NW waves stages the B fragments
+// to LDS once ([step][tile][lane], one conflict-free ds_read_b32 per MFMA)
+// and its waves then walk tiles grid-stride with no further barrier.
+// A fragments come straight from global (lane (i, kk) reads
+// in[x0+i][4s+kk]; the C/4 loads of a tile cover its contiguous 16*C
+// floats). The accumulators leave through a wave-private LDS bounce
+// [16 positions][4K + 4]: for a parity row py the tile's outputs are ONE
+// contiguous run of 32K floats in output row 2y+py (position i holds the
+// 2K floats (px, k) at bounce[i][py*2K ..]), so `out` and `skip` move as
+// 16-byte accesses, K/4 per lane per tile. The +4 row pad spreads the
+// accumulator's four row groups over the banks.
+//
+// Memory pipeline: a tile's skip loads and the NEXT tile's A loads are
+// issued as one batch, from clamped addresses and with no branch around
+// them, before the tile's MFMAs; they are the newest entries of vmcnt, so
+// the MFMAs wait only for A values loaded a tile earlier and the epilogue's
+// wait for the skip values counts the A prefetch behind them, never a
+// drain (loads and stores share vmcnt; conv.hip's z-ring epilogue records
+// the lesson). Partial tiles select at the store. The skip add is the last
+// f32 add on the finished value, so the fused call equals the unfused
+// kernel + a separate add bit for bit.
+
+// waves per workgroup, one per SIMD. Workgroups pack onto a CU as
+// registers and LDS allow: the 36 -> 28 kernel with skip (220 VGPRs +
+// AGPRs, 46 KB) runs two, i.e. 2 waves per SIMD, which with the loads
+// issued a phase ahead reaches 5.6 TB/s (profiles/upskip_probe.json)
+constexpr int UM_NW = 4;
+
+typedef float um_f32x4 __attribute__((ext_vector_type(4)));
+
+template <int NT, bool SKIP>  // K = 4 * NT
+__global__ __launch_bounds__(UM_NW * 64) void k_upconv2_mfma(
+    const float* __restrict__ in, const float* __restrict__ wgt,
+    const float* __restrict__ bias, const float* __restrict__ skip,
+    float* __restrict__ out, int W, int C, int xtiles, int ntiles) {
+    constexpr int K = 4 * NT;
+    constexpr int N4 = 4 * K;     // GEMM N
+    constexpr int BS = N4 + 4;    // bounce row stride, dwords
+    constexpr int RUN4 = 2 * NT;  // 16-byte pieces per position per py
+    extern __shared__ __attribute__((aligned(16))) float um_smem[];
+    const int S = C >> 2;         // MFMA steps
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    float* s_w = um_smem;                               // [S][NT][64]
+    float* s_b = um_smem + C * N4 + wave * (16 * BS);   // [16][BS]
+
+    // B[k = lane>>4][j = lane&15] of (step s, tile t)
+    for (int idx = tid; idx < C * N4; idx += UM_NW * 64) {
+        const int l = idx & 63;
+        const int st = idx >> 6;
+        const int t = st % NT;
+        const int s = st / NT;
+        const int c = 4 * s + (l >> 4);
+        const int col = 16 * t + (l & 15);
+        const int q = col / K;
+        s_w[idx] = wgt[(q * C + c) * K + (col - q * K)];
+    }
+    __syncthreads();
+
+    const int ai = lane & 15;   // A row / D column
+    const int akk = lane >> 4;  // A k / D row group
+    float bj[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+        bj[t] = bias ? bias[(16 * t + ai) % K] : 0.f;
+
+    // epilogue piece `it` of this lane: f = it*64 + lane over
+    // [py][position i][RUN4 pieces]
+    auto piece = [&](int it, int& py, int& i, int& j4) {
+        const int f = it * 64 + lane;
+        py = f >= 16 * RUN4;
+        const int rem = f - py * (16 * RUN4);
+        i = rem / RUN4;
+        j4 = rem - i * RUN4;
+    };
+    // global loads, branch-free, 32-bit lane offsets on wave-uniform tile
+    // bases: the A fragments of a tile ...
+    auto a_loads = [&](int tile, float (&a)[16]) {
+        const int xt = tile % xtiles;
+        const long long row = tile / xtiles;  // (n*D + z)*H + y
+        const int x0 = xt * 16;
+        const int ilast = min(16, W - x0) - 1;
+        const float* ip = in + (row * W + x0) * C;
+        const unsigned ao = min(ai, ilast) * C + akk;
+#pragma unroll
+        for (int s = 0; s < 16; ++s) a[s] = ip[ao + 4u * min(s, S - 1)];
+    };
+    // ... and its skip values, in the epilogue's piece order
+    auto skip_loads = [&](int tile, um_f32x4 (&sv)[NT]) {
+        const int xt = tile % xtiles;
+        const long long row = tile / xtiles;
+        const int x0 = xt * 16;
+        const int ilast = min(16, W - x0) - 1;
+        const float* sp = skip + (2 * row * 2 * W + 2 * x0) * K;
+#pragma unroll
+        for (int it = 0; it < NT; ++it) {
+            int py, i, j4;
+            piece(it, py, i, j4);
+            const unsigned so =
+                py * (2 * W * K) + min(i, ilast) * (2 * K) + 4 * j4;
+            sv[it] = *reinterpret_cast<const um_f32x4*>(sp + so);
+        }
+    };
+
+    // one tile: its skip loads and the next tile's A loads fly over the
+    // MFMAs on `a`
+    auto do_tile = [&](int tile, int next, const float (&a)[16],
+                       float (&a2)[16]) {
+        um_f32x4 sv[NT];
+        if (SKIP) skip_loads(tile, sv);
+        a_loads(next, a2);
+        __builtin_amdgcn_sched_barrier(0);
+        um_f32x4 acc[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+            acc[t] = um_f32x4{bj[t], bj[t], bj[t], bj[t]};
+#pragma unroll
+        for (int s = 0; s < 16; ++s) {
+            if (s >= S) break;
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+                acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                    a[s], s_w[(s * NT + t) * 64 + lane], acc[t], 0, 0, 0);
+        }
+        // D[row = akk*4 + r][col = ai] -> bounce[position][q*K + k]
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                s_b[(akk * 4 + r) * BS + 16 * t + ai] = acc[t][r];
+        __builtin_amdgcn_wave_barrier();
+
+        const int xt = tile % xtiles;
+        const long long row = tile / xtiles;
+        const int x0 = xt * 16;
+        const int nvalid = min(16, W - x0);
+        float* op = out + (2 * row * 2 * W + 2 * x0) * K;
+        // every output finished in registers first, then the stores go
+        // out back to back
+        um_f32x4 v[NT];
+#pragma unroll
+        for (int it = 0; it < NT; ++it) {
+            int py, i, j4;
+            piece(it, py, i, j4);
+            v[it] = *reinterpret_cast<const um_f32x4*>(
+                &s_b[i * BS + py * (2 * K) + 4 * j4]);
+            if (SKIP) v[it] += sv[it];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int it = 0; it < NT; ++it) {
+            int py, i, j4;
+            piece(it, py, i, j4);
+            const unsigned oo = py * (2 * W * K) + i * (2 * K) + 4 * j4;
+            if (nvalid == 16 || i < nvalid)
+                *reinterpret_cast<um_f32x4*>(op + oo) = v[it];
+        }
+        __builtin_amdgcn_wave_barrier();  // bounce is rewritten next tile
+    };
+
+    // two tiles per trip, the A register sets swapping roles (a copy at
+    // the loop end would wait for the prefetch it copies)
+    const int stride = gridDim.x * UM_NW;
+    int tile = blockIdx.x * UM_NW + wave;
+    if (tile >= ntiles) return;
+    float a0[16], a1[16];
+    a_loads(tile, a0);
+    while (true) {
+        do_tile(tile, min(tile + stride, ntiles - 1), a0, a1);
+        tile += stride;
+        if (tile >= ntiles) break;
+        do_tile(tile, min(tile + stride, ntiles - 1), a1, a0);
+        tile += stride;
+        if (tile >= ntiles) break;
     }
 }
 
@@ -536,6 +729,47 @@ __global__ __launch_bounds__(256, 2) void k_conv155_out_mfma(
     }
 }
 
+// ---- one-pass epilogue for the convs left on MIOpen ----------------------
+// y[v][k] = act(y[v][k] + bias[k] (+ res[v][k])), in place on an NDHWC f32
+// tensor: the bias pass, the residual add and the ELU that torch runs as
+// separate full-tensor kernels behind a MIOpen conv. ELU as in the ring
+// epilogue: expm1f of the non-positive part, then a select (NaN stays NaN).
+__device__ __forceinline__ float bre_act(float v, int do_elu) {
+    if (do_elu) {
+        const float e = expm1f(v > 0.f ? 0.f : v);
+        v = v > 0.f ? v : e;
+    }
+    return v;
+}
+
+template <bool VEC>  // VEC: K % 4 == 0 and 16-byte aligned tensors
+__global__ __launch_bounds__(256) void k_bias_res_elu(
+    float* __restrict__ y, const float* __restrict__ bias,
+    const float* __restrict__ res, long long total, int K, int do_elu) {
+    const long long step = (long long)gridDim.x * 256;
+    long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (VEC) {
+        const long long n4 = total >> 2;
+        const int K4 = K >> 2;
+        for (; i < n4; i += step) {
+            const int k4 = (int)(i % K4);
+            um_f32x4 v = reinterpret_cast<const um_f32x4*>(y)[i];
+            if (bias) v += reinterpret_cast<const um_f32x4*>(bias)[k4];
+            if (res) v += reinterpret_cast<const um_f32x4*>(res)[i];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = bre_act(v[e], do_elu);
+            reinterpret_cast<um_f32x4*>(y)[i] = v;
+        }
+    } else {
+        for (; i < total; i += step) {
+            float v = y[i];
+            if (bias) v += bias[(int)(i % K)];
+            if (res) v += res[i];
+            y[i] = bre_act(v, do_elu);
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int cfx_conv155_out(cfx_ctx* ctx, const void* in,
@@ -606,12 +840,114 @@ extern "C" int cfx_conv155_c1(cfx_ctx* ctx, const void* in, const void* wgt,
     return 0;
 }
 
+namespace {
+
+// LDS of k_upconv2_mfma: the B fragments + one bounce per wave
+size_t um_shmem(int C, int K) {
+    return ((size_t)C * 4 * K + (size_t)UM_NW * 16 * (4 * K + 4)) *
+           sizeof(float);
+}
+
+// shapes the MFMA up-conv takes: whole MFMA steps and 16-byte channel
+// runs, 16-byte aligned tensors, a tile count that fits an int; K <= 48
+// (NT <= 12, RSUNet's widest up-conv) is instantiated -- there the
+// accumulators, the skip batch and the two A sets already take 195 VGPRs
+// + 144 AGPRs, one wave per SIMD
+bool um_eligible(const void* in, const void* skip, const void* out, int N,
+                 int D, int H, int W, int C, int K) {
+    return C % 4 == 0 && K % 4 == 0 && C >= 4 && C <= 64 && K >= 4 &&
+           K <= 48 && (((size_t)in | (size_t)skip | (size_t)out) & 15) == 0 &&
+           (long long)N * D * H * ((W + 15) / 16) < (1LL << 31);
+}
+
+template <int NT, bool SKIP>
+int um_launch_nt(cfx_ctx* ctx, const float* in, const float* wgt,
+                 const float* bias, const float* skip, float* out, int W,
+                 int C, int xtiles, int ntiles) {
+    const size_t shmem = um_shmem(C, 4 * NT);
+    if (shmem > 64 * 1024)
+        CFX_CHECK(hipFuncSetAttribute(
+            reinterpret_cast<const void*>(&k_upconv2_mfma<NT, SKIP>),
+            hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+    int cus = 0;
+    CFX_CHECK(hipDeviceGetAttribute(
+        &cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    // persistent: as many workgroups as the LDS lets a CU hold
+    const int per_cu = (int)std::min<size_t>(8, (160 * 1024) / shmem);
+    const int grid =
+        std::min((ntiles + UM_NW - 1) / UM_NW, std::max(1, cus * per_cu));
+    hipLaunchKernelGGL((k_upconv2_mfma<NT, SKIP>), dim3(grid),
+                       dim3(UM_NW * 64), shmem, ctx->stream, in, wgt, bias,
+                       skip, out, W, C, xtiles, ntiles);
+    CFX_CHECK(hipGetLastError());
+    return 0;
+}
+
+template <bool SKIP>
+int um_launch(cfx_ctx* ctx, const float* in, const float* wgt,
+              const float* bias, const float* skip, float* out, int N,
+              int D, int H, int W, int C, int K) {
+    const int xtiles = (W + 15) / 16;
+    const int ntiles = N * D * H * xtiles;
+    if (ntiles == 0) return 0;
+    switch (K / 4) {
+#define UM_CASE(NT)                                                         \
+    case NT:                                                                \
+        return um_launch_nt<NT, SKIP>(ctx, in, wgt, bias, skip, out, W, C,  \
+                                      xtiles, ntiles);
+        UM_CASE(1) UM_CASE(2) UM_CASE(3) UM_CASE(4) UM_CASE(5) UM_CASE(6)
+        UM_CASE(7) UM_CASE(8) UM_CASE(9) UM_CASE(10) UM_CASE(11)
+        UM_CASE(12)
+#undef UM_CASE
+    }
+    g_err = "upconv mfma: K not instantiated";
+    return -1;
+}
+
+}  // namespace
+
+extern "C" int cfx_upconv_2x2_add(cfx_ctx* ctx, const void* in,
+                                  const void* wgt, const float* bias,
+                                  const void* skip, void* out, int N, int D,
+                                  int H, int W, int C, int K, int is_bf16) {
+    if (!skip)
+        return cfx_upconv_2x2(ctx, in, wgt, bias, out, N, D, H, W, C, K,
+                              is_bf16);
+    if (is_bf16) {
+        g_err = "cfx_upconv_2x2_add: skip is f32 only";
+        return -1;
+    }
+    if (!um_eligible(in, skip, out, N, D, H, W, C, K)) {
+        g_err = "cfx_upconv_2x2_add: skip needs C % 4 == 0, K % 4 == 0, "
+                "C <= 64, K <= 48 and 16-byte aligned tensors";
+        return -1;
+    }
+    hipEvent_t e0;
+    if (prof_begin(ctx, &e0)) return -1;
+    if (um_launch<true>(ctx, (const float*)in, (const float*)wgt, bias,
+                        (const float*)skip, (float*)out, N, D, H, W, C, K))
+        return -1;
+    double flops = 2.0 * 4.0 * C * K * (double)N * D * H * W;
+    if (prof_end(ctx, e0, CFX_K_CONV_STREAM, flops)) return -1;
+    return 0;
+}
+
 extern "C" int cfx_upconv_2x2(cfx_ctx* ctx, const void* in, const void* wgt,
                               const float* bias, void* out, int N, int D,
                               int H, int W, int C, int K, int is_bf16) {
     if (K > 64 || C > 64) {
         g_err = "cfx_upconv_2x2: C, K <= 64 supported";
         return -1;
+    }
+    if (!is_bf16 && um_eligible(in, nullptr, out, N, D, H, W, C, K)) {
+        hipEvent_t e0;
+        if (prof_begin(ctx, &e0)) return -1;
+        if (um_launch<false>(ctx, (const float*)in, (const float*)wgt, bias,
+                             nullptr, (float*)out, N, D, H, W, C, K))
+            return -1;
+        double flops = 2.0 * 4.0 * C * K * (double)N * D * H * W;
+        if (prof_end(ctx, e0, CFX_K_CONV_STREAM, flops)) return -1;
+        return 0;
     }
     constexpr int XI = 64;
     dim3 grid((W + XI - 1) / XI, H, (unsigned)(N * D));
@@ -664,5 +1000,30 @@ extern "C" int cfx_downconv_2x2(cfx_ctx* ctx, const void* in,
     CFX_CHECK(hipGetLastError());
     double flops = 2.0 * 4.0 * C * K * (double)N * D * (H / 2) * (W / 2);
     if (prof_end(ctx, e0, CFX_K_CONV_STREAM, flops)) return -1;
+    return 0;
+}
+
+extern "C" int cfx_bias_res_elu(cfx_ctx* ctx, float* y, const float* bias,
+                                const float* res, long long nvox, int K,
+                                int do_elu) {
+    if (nvox < 0 || K < 1) {
+        g_err = "cfx_bias_res_elu: nvox >= 0, K >= 1";
+        return -1;
+    }
+    const long long total = nvox * K;
+    if (total == 0) return 0;
+    const bool vec =
+        K % 4 == 0 &&
+        (((size_t)y | (size_t)bias | (size_t)res) & 15) == 0;
+    const long long items = vec ? total / 4 : total;
+    // a few resident workgroups per CU, grid-stride
+    const int grid = (int)std::min<long long>((items + 255) / 256, 256 * 16);
+    if (vec)
+        hipLaunchKernelGGL((k_bias_res_elu<true>), dim3(grid), dim3(256), 0,
+                           ctx->stream, y, bias, res, total, K, do_elu);
+    else
+        hipLaunchKernelGGL((k_bias_res_elu<false>), dim3(grid), dim3(256), 0,
+                           ctx->stream, y, bias, res, total, K, do_elu);
+    CFX_CHECK(hipGetLastError());
     return 0;
 }

@@ -74,6 +74,13 @@ class PyTorchEngine(EngineBase):
                 from ..fastconv import accelerate_conv_out
                 self.fastconv_count += accelerate_conv_out(
                     self.model, idx, bf16=bf)
+                # the decoder's `up(x) + skip` adds move into the up-conv's
+                # epilogue (torch.fx rewrite, f32 only; guarded)
+                self.upskip_count = 0
+                if not bf:
+                    from ..fastconv import accelerate_up_skip
+                    self.model, self.upskip_count = accelerate_up_skip(
+                        self.model, idx, self.num_input_channels)
         torch.backends.cudnn.benchmark = True
         self.pre_process = getattr(net_source, 'pre_process', None)
         self.post_process = getattr(net_source, 'post_process', None)

@@ -6,6 +6,12 @@ in_channels == out_channels in {28, 36, 48, 64} — the RSUNet ResBlock
 convs, ~85% of the affinity UNet's FLOPs. Everything else stays on
 MIOpen. Enabled in the pytorch engine via CFX_FASTCONV (see engine);
 weights are repacked once to the kernel's (27, C, K) tap-major layout.
+
+Further down: the up/down-sampling and (1,5,5) conv swaps
+(csrc/updown.hip), the torch.fx pass that moves the decoder's
+`up(x) + skip` add into the up-conv's epilogue (fuse_up_skip_adds), and
+CfxMiopenResBlock, which gives the ResBlocks whose convs stay on MIOpen a
+one-pass bias / residual / ELU epilogue.
 """
 import os
 
@@ -103,13 +109,73 @@ def _resblock_like(m: nn.Module) -> bool:
             and _eligible(m.conv1) and _eligible(m.conv2))
 
 
+def _conv333(m: nn.Module) -> bool:
+    return (isinstance(m, nn.Conv3d)
+            and m.kernel_size == (3, 3, 3)
+            and m.stride == (1, 1, 1)
+            and m.padding == (1, 1, 1)
+            and m.dilation == (1, 1, 1)
+            and m.groups == 1
+            and m.in_channels == m.out_channels)
+
+
+class CfxMiopenResBlock(nn.Module):
+    """The RSUNet ResBlock pattern at the widths whose 3x3x3 convs stay on
+    MIOpen (not in ELIGIBLE_WIDTHS): the convs run without bias, so torch
+    launches no bias pass, and one in-place stream kernel per conv
+    (csrc/updown.hip k_bias_res_elu) does bias + ELU, resp. bias +
+    residual + ELU -- instead of a bias pass, an ELU pass and an add pass
+    over the full tensor. f32 only."""
+
+    def __init__(self, block: nn.Module, device_index: int = 0):
+        super().__init__()
+        self.C = block.conv1.in_channels
+        self.device_index = device_index
+        for i, conv in ((1, block.conv1), (2, block.conv2)):
+            self.register_buffer(f'w{i}', conv.weight.detach())
+            self.register_buffer(
+                f'b{i}', conv.bias.detach().float().contiguous()
+                if conv.bias is not None else None)
+
+    def _conv(self, x, w, b, res):
+        y = torch.nn.functional.conv3d(x, w, None, padding=1)
+        y = y.contiguous(memory_format=torch.channels_last_3d)
+        n, k, d, h, wd = y.shape
+        get_cfx(self.device_index).bias_res_elu(
+            y.data_ptr(), b.data_ptr() if b is not None else None,
+            res.data_ptr() if res is not None else None,
+            n * d * h * wd, k, do_elu=True)
+        return y
+
+    def forward(self, x):
+        assert x.dtype == torch.float32, 'fastconv is the f32 path'
+        x = x.contiguous(memory_format=torch.channels_last_3d)
+        h = self._conv(x, self.w1, self.b1, None)
+        return self._conv(h, self.w2, self.b2, x)
+
+
+def _miopen_resblock_like(m: nn.Module) -> bool:
+    return (hasattr(m, 'conv1') and hasattr(m, 'conv2')
+            and isinstance(getattr(m, 'act', None), nn.ELU)
+            and getattr(m.act, 'alpha', None) == 1.0
+            and not isinstance(m, (CfxConv3d, CfxResBlock,
+                                   CfxMiopenResBlock))
+            and _conv333(m.conv1) and _conv333(m.conv2)
+            and m.conv1.in_channels == m.conv2.in_channels
+            and not _eligible(m.conv1) and not _eligible(m.conv2))
+
+
 @torch.no_grad()
-def _fusion_matches(block: nn.Module, fused: 'CfxResBlock') -> bool:
+def _fusion_matches(block: nn.Module, fused: nn.Module) -> bool:
     """Functional probe at surgery time: the fused block must reproduce the
     original forward on a random input (guards against user modules that
     merely LOOK like a ResBlock)."""
-    C = fused.c1.C
-    x = torch.randn(1, C, 4, 18, 22, device=fused.c1.wtap.device)         .contiguous(memory_format=torch.channels_last_3d)
+    if isinstance(fused, CfxMiopenResBlock):
+        C, dev = fused.C, fused.w1.device
+    else:
+        C, dev = fused.c1.C, fused.c1.wtap.device
+    x = torch.randn(1, C, 4, 18, 22, device=dev) \
+        .contiguous(memory_format=torch.channels_last_3d)
     want = block.to(x.device)(x)
     got = fused(x)
     return bool(torch.allclose(got, want, rtol=1e-4, atol=1e-4))
@@ -137,6 +203,12 @@ def maybe_accelerate(model: nn.Module, device_index: int = 0) -> int:
                     setattr(child, cn,
                             CfxConv3d(getattr(child, cn),
                                       device_index).to(dev))
+                    count += 1
+            elif _miopen_resblock_like(child):
+                fused = CfxMiopenResBlock(child, device_index).to(dev)
+                if _fusion_matches(child, fused):
+                    setattr(parent, name, fused)
+                    fused_out.add(id(child))
                     count += 1
             elif _eligible(child):
                 setattr(parent, name,
@@ -288,7 +360,23 @@ class CfxUpConv3d(nn.Module):
         else:
             self.bias = None
 
-    def forward(self, x):
+    def _fusable(self, skip, out_shape) -> bool:
+        """The kernel adds `skip` in its epilogue when it is what the
+        f32 MFMA up-conv streams: f32, channels-last contiguous, of the
+        output's shape, 16-byte aligned (csrc/updown.hip um_eligible)."""
+        return (not self.bf16 and torch.is_tensor(skip)
+                and skip.dtype == torch.float32
+                and skip.device == self.wpack.device
+                and tuple(skip.shape) == tuple(out_shape)
+                and skip.is_contiguous(
+                    memory_format=torch.channels_last_3d)
+                and skip.data_ptr() % 16 == 0
+                and self.C % 4 == 0 and self.K % 4 == 0
+                and self.C <= 64 and self.K <= 48)
+
+    def forward(self, x, skip=None):
+        """up(x), or up(x) + skip. The sum is bit-identical either way:
+        fused, the add is the kernel's last f32 operation."""
         x = x.contiguous(memory_format=torch.channels_last_3d)
         n, c, d, h, w = x.shape
         dt = torch.bfloat16 if self.bf16 else torch.float32
@@ -296,10 +384,15 @@ class CfxUpConv3d(nn.Module):
         out = torch.empty((n, self.K, d, 2 * h, 2 * w), dtype=dt,
                           device=x.device,
                           memory_format=torch.channels_last_3d)
-        get_cfx(self.device_index).upconv_2x2(
+        fuse = (skip is not None and self._fusable(skip, out.shape)
+                and x.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0)
+        get_cfx(self.device_index).upconv_2x2_add(
             x.data_ptr(), self.wpack.data_ptr(),
             self.bias.data_ptr() if self.bias is not None else None,
+            skip.data_ptr() if fuse else None,
             out.data_ptr(), n, d, h, w, self.C, self.K, bf16=self.bf16)
+        if skip is not None and not fuse:
+            return out + skip
         return out
 
 
@@ -337,20 +430,25 @@ class CfxDownConv3d(nn.Module):
         return out
 
 
-# surgery allowlist (measured, profiles/updown_probe_r02.json): the hand
-# up-conv wins at in_channels 36 (7.1x bf16 / 2.1x f32) and 48 (tie bf16 /
-# 1.4x f32); it loses at 64 (32^2 extent) and the down shapes lose to
-# MIOpen everywhere (0.03-0.25x) -- those keep MIOpen; kernels stay
-# callable and GPU-tested for the record.
+# surgery allowlist. bf16 (measured, profiles/updown_probe_r02.json): the
+# hand up-conv wins at in_channels 36 (7.1x) and ties at 48; it loses at 64
+# (32^2 extent). f32 (profiles/upskip_probe.json, 12 x 20 patches, up +
+# skip-add): the MFMA up-conv with the add in its epilogue takes 0.73 ms
+# at 36 (5.6 TB/s; VALU kernel + torch add 2.0 ms), 0.26 ms at 48 (0.86)
+# and 0.09 ms at 64, where MIOpen + bias pass + add took 0.31 -- all three
+# levels are on. The down shapes lose to MIOpen everywhere (0.03-0.25x)
+# and keep it; kernels stay callable and GPU-tested for the record.
 UP_SURGERY_WIDTHS = (36, 48)
+UP_SURGERY_WIDTHS_F32 = (36, 48, 64)
 
 
-def _up_eligible(m) -> bool:
+def _up_eligible(m, bf16: bool = False) -> bool:
+    widths = UP_SURGERY_WIDTHS if bf16 else UP_SURGERY_WIDTHS_F32
     return (isinstance(m, nn.ConvTranspose3d)
             and m.kernel_size == (1, 2, 2) and m.stride == (1, 2, 2)
             and m.padding == (0, 0, 0) and m.output_padding == (0, 0, 0)
             and m.dilation == (1, 1, 1) and m.groups == 1
-            and m.in_channels in UP_SURGERY_WIDTHS
+            and m.in_channels in widths
             and m.out_channels <= 64)
 
 
@@ -382,12 +480,103 @@ def accelerate_updown(model: nn.Module, device_index: int = 0,
     for parent in list(model.modules()):
         for name, child in list(parent.named_children()):
             repl = None
-            if _up_eligible(child):
+            if _up_eligible(child, bf16):
                 repl = CfxUpConv3d(child, device_index, bf16=bf16).to(dev)
             if repl is not None and _updown_matches(child, repl, dev, bf16):
                 setattr(parent, name, repl)
                 count += 1
     return count
+
+
+def fuse_up_skip_adds(model: nn.Module, is_up=None):
+    """torch.fx pass: rewrite `up(x) + other` to `up(x, other)` so the
+    decoder's skip-add runs in the up-conv's epilogue. The add lives in
+    the user's forward, out of module surgery's reach, so the root is
+    traced with every non-container submodule as a leaf. A node matches
+    when it is operator.add / torch.add / Tensor.add of two operands (no
+    alpha), one of them the output of a module `is_up` accepts (default:
+    CfxUpConv3d) called with one argument, and that output has no other
+    user. Returns (model, count): a GraphModule sharing the original's
+    submodules, or the model itself when nothing matched or it cannot be
+    traced (e.g. tensor-dependent control flow)."""
+    import operator
+
+    import torch.fx as fx
+
+    if is_up is None:
+        def is_up(m):
+            return isinstance(m, CfxUpConv3d)
+
+    class _Tracer(fx.Tracer):
+        def is_leaf_module(self, m, qualname):
+            return not isinstance(m, (nn.ModuleList, nn.ModuleDict,
+                                      nn.Sequential))
+
+    try:
+        graph = _Tracer().trace(model)
+    except Exception:
+        return model, 0
+    mods = dict(model.named_modules())
+
+    def up_call(n):
+        return (isinstance(n, fx.Node) and n.op == 'call_module'
+                and is_up(mods.get(n.target)) and len(n.args) == 1
+                and not n.kwargs and len(n.users) == 1)
+
+    count = 0
+    for node in list(graph.nodes):
+        is_add = (node.op == 'call_function'
+                  and node.target in (operator.add, torch.add)) or \
+                 (node.op == 'call_method' and node.target == 'add')
+        if not is_add or len(node.args) != 2 or node.kwargs:
+            continue
+        a, b = node.args
+        if up_call(a) and isinstance(b, fx.Node) and b is not a:
+            up, other = a, b
+        elif up_call(b) and isinstance(a, fx.Node) and a is not b:
+            up, other = b, a
+        else:
+            continue
+        # the rewrite makes `other` an input of the up call: it has to
+        # be computed before it
+        order = {n: i for i, n in enumerate(graph.nodes)}
+        if order[other] > order[up]:
+            continue
+        up.args = (up.args[0], other)
+        node.replace_all_uses_with(up)
+        graph.erase_node(node)
+        count += 1
+    if count == 0:
+        return model, 0
+    try:
+        graph.lint()
+        return fx.GraphModule(model, graph), count
+    except Exception:
+        return model, 0
+
+
+@torch.no_grad()
+def accelerate_up_skip(model: nn.Module, device_index: int = 0,
+                       in_channels: int = 1):
+    """Run fuse_up_skip_adds on an f32 model after the module surgery and
+    keep the rewrite only if it reproduces the model on two small inputs
+    of different spatial size (two sizes catch a trace that baked a shape
+    in). Returns (model, fused add count); on any failure the model comes
+    back as it was."""
+    dev = f'cuda:{device_index}'
+    try:
+        fused, count = fuse_up_skip_adds(model)
+        if count == 0:
+            return model, 0
+        for shape in ((2, 16, 24), (3, 32, 16)):
+            x = torch.randn(1, in_channels, *shape, device=dev).contiguous(
+                memory_format=torch.channels_last_3d)
+            if not torch.allclose(fused(x), model(x), rtol=1e-4,
+                                  atol=1e-4):
+                return model, 0
+        return fused, count
+    except Exception:
+        return model, 0
 
 
 class CfxConvIn155(nn.Module):

@@ -31,8 +31,8 @@ SYMBOLS = [
     'cfx_downsample_mode2', 'cfx_downsample_mode3',
     'cfx_conv3_ndhwc', 'cfx_conv3_ndhwc_w32',
     'cfx_conv3_ndhwc_zring', 'cfx_conv3_ndhwc_bf16',
-    'cfx_upconv_2x2', 'cfx_downconv_2x2', 'cfx_conv155_c1',
-    'cfx_conv155_out',
+    'cfx_upconv_2x2', 'cfx_upconv_2x2_add', 'cfx_downconv_2x2',
+    'cfx_conv155_c1', 'cfx_conv155_out', 'cfx_bias_res_elu',
     'cfx_profile_enable', 'cfx_profile_reset',
     'cfx_profile_get',
 ]
@@ -327,6 +327,29 @@ class CfxContext:
             ctypes.c_int(h), ctypes.c_int(w), ctypes.c_int(c),
             ctypes.c_int(k), ctypes.c_int(1 if bf16 else 0)),
             'cfx_upconv_2x2')
+
+    def upconv_2x2_add(self, in_ptr, wgt_ptr, bias_ptr, skip_ptr, out_ptr,
+                       n, d, h, w, c, k, bf16=False):
+        """up-conv with `skip` (f32 NDHWC, the output's shape) added in
+        the kernel's epilogue; skip_ptr None is upconv_2x2."""
+        self._chk(self.lib.cfx_upconv_2x2_add(
+            ctypes.c_void_p(self.ctx), ctypes.c_void_p(in_ptr),
+            ctypes.c_void_p(wgt_ptr),
+            ctypes.c_void_p(bias_ptr) if bias_ptr else None,
+            ctypes.c_void_p(skip_ptr) if skip_ptr else None,
+            ctypes.c_void_p(out_ptr), ctypes.c_int(n), ctypes.c_int(d),
+            ctypes.c_int(h), ctypes.c_int(w), ctypes.c_int(c),
+            ctypes.c_int(k), ctypes.c_int(1 if bf16 else 0)),
+            'cfx_upconv_2x2_add')
+
+    def bias_res_elu(self, y_ptr, bias_ptr, res_ptr, nvox, k, do_elu=True):
+        """in place on NDHWC f32 y: y = act(y + bias (+ res))"""
+        self._chk(self.lib.cfx_bias_res_elu(
+            ctypes.c_void_p(self.ctx), ctypes.c_void_p(y_ptr),
+            ctypes.c_void_p(bias_ptr) if bias_ptr else None,
+            ctypes.c_void_p(res_ptr) if res_ptr else None,
+            ctypes.c_longlong(nvox), ctypes.c_int(k),
+            ctypes.c_int(1 if do_elu else 0)), 'cfx_bias_res_elu')
 
     def downconv_2x2(self, in_ptr, wgt_ptr, bias_ptr, out_ptr, n, d, h, w,
                      c, k, bf16=False):

@@ -231,10 +231,29 @@ int cfx_conv3_ndhwc_bf16(cfx_ctx* ctx, const void* in, const void* wgt,
 /* ---- up/down-sampling convs (RSUNet (1,2,2)-kernel, (1,2,2)-stride) ----- */
 /* ConvTranspose3d: out (N,D,2H,2W,K) from in (N,D,H,W,C), NDHWC; wgt
  * packed [parity q=(py<<1)|px][C][K] in the compute dtype; bias f32 or
- * NULL; is_bf16 selects bf16 vs f32 tensors. HBM-streaming VALU kernel. */
+ * NULL; is_bf16 selects bf16 vs f32 tensors. HBM-streaming kernels: f32
+ * shapes with C % 4 == 0, K % 4 == 0, K <= 48 run on the f32 MFMA, the
+ * rest (and bf16) on the VALU kernel. */
 int cfx_upconv_2x2(cfx_ctx* ctx, const void* in, const void* wgt,
                    const float* bias, void* out, int N, int D, int H,
                    int W, int C, int K, int is_bf16);
+/* the same transposed conv with the decoder's skip-add in its epilogue:
+ * out = (bias + sum_c in * w) + skip, skip an f32 NDHWC tensor of out's
+ * shape; the add is the last f32 operation, so the result equals
+ * cfx_upconv_2x2 followed by a separate add bit for bit. skip == NULL is
+ * cfx_upconv_2x2. With skip: f32 only (is_bf16 is an error), C % 4 == 0,
+ * K % 4 == 0, C <= 64, K <= 48, in/skip/out 16-byte aligned -- the shapes
+ * of the f32 MFMA kernel, which cfx_upconv_2x2 also takes for them */
+int cfx_upconv_2x2_add(cfx_ctx* ctx, const void* in, const void* wgt,
+                       const float* bias, const void* skip, void* out,
+                       int N, int D, int H, int W, int C, int K,
+                       int is_bf16);
+/* one-pass epilogue behind a bias-free MIOpen conv: in place on the NDHWC
+ * f32 tensor y (nvox positions x K channels),
+ * y = act(y + bias[k] (+ res)), act = ELU(alpha=1) if do_elu; bias and
+ * res (y's layout) may be NULL. Not timed into any profile slot. */
+int cfx_bias_res_elu(cfx_ctx* ctx, float* y, const float* bias,
+                     const float* res, long long nvox, int K, int do_elu);
 /* strided Conv3d (downsample): out (N,D,H/2,W/2,K) from in (N,D,H,W,C);
  * same wgt pack/convention as cfx_upconv_2x2 */
 int cfx_downconv_2x2(cfx_ctx* ctx, const void* in, const void* wgt,

@@ -2,6 +2,15 @@
 up/down-sampling convs (csrc/updown.hip) and the sliced bf16 ring
 (C=36/48). Drained-queue timing (tools/conv_probe.py lesson). Writes JSON
 to gpurun_out/updown_probe.json."""
+# Two further modes:
+# `--upskip OUT.json` instead times the decoder's up-conv + skip-add at the
+# three config-2 levels: (a) the tree's up path (hand kernel where surgery
+# takes the width, MIOpen otherwise) followed by the torch add, and, in a
+# tree whose CfxUpConv3d takes a skip, (b) the fused call. Run it from the
+# parent and the changed tree in turn for an alternated A/B.
+# `--miopen-block OUT.json` times one C=48 ResBlock at 12 x 20 x 64^2 as
+# torch runs it (MIOpen conv + bias pass, ELU pass, add pass) against
+# CfxMiopenResBlock (bias-free conv + one in-place epilogue), alternated.
 import json
 import os
 import sys
@@ -118,7 +127,102 @@ def probe_conv155_out(N, D, H, W, bf16):
     print(name, RES[name], flush=True)
 
 
+def probe_upskip(path, rounds=3):
+    """f32 up-conv + skip-add at 12 x 20 x {128^2, 64^2, 32^2}; TB/s is
+    (in + skip + out bytes) / time, the traffic the fused result needs."""
+    import inspect
+    import chunkflow_amd.fastconv as fc
+    UP_SURGERY_WIDTHS = getattr(fc, 'UP_SURGERY_WIDTHS_F32',
+                                fc.UP_SURGERY_WIDTHS)
+    fusable = 'skip' in inspect.signature(CfxUpConv3d.forward).parameters
+    res = {'fused_available': fusable,
+           'up_surgery_widths': list(UP_SURGERY_WIDTHS)}
+    N, D = 12, 20
+    for C, K, H in ((36, 28, 128), (48, 36, 64), (64, 48, 32)):
+        torch.manual_seed(0)
+        conv = nn.ConvTranspose3d(C, K, (1, 2, 2), stride=(1, 2, 2)).cuda()
+        hand = CfxUpConv3d(conv, 0, bf16=False).cuda()
+        tconv = conv.to(memory_format=cl)
+        x = torch.randn(N, C, D, H, H, device='cuda').contiguous(
+            memory_format=cl)
+        skip = torch.randn(N, K, D, 2 * H, 2 * H, device='cuda').contiguous(
+            memory_format=cl)
+        nbytes = 4 * (x.numel() + 2 * skip.numel())
+        up = hand if C in UP_SURGERY_WIDTHS else tconv
+        entry = {'bytes_in_skip_out': nbytes, 'unfused_ms': [],
+                 'unfused_path': 'hand' if up is hand else 'miopen'}
+        with torch.no_grad():
+            want = tconv(x) + skip
+            entry['unfused_max_err'] = \
+                (up(x) + skip - want).abs().max().item()
+            if fusable:
+                entry['fused_ms'] = []
+                entry['hand_unfused_ms'] = []
+                got = hand(x, skip)
+                entry['fused_max_err'] = (got - want).abs().max().item()
+                entry['fused_bitwise_eq_hand_plus_add'] = bool(
+                    torch.equal(got, hand(x) + skip))
+            for _ in range(rounds):  # alternated inside the tree too
+                entry['unfused_ms'].append(
+                    timeit(lambda: up(x) + skip, 20) * 1e3)
+                if fusable:
+                    entry['fused_ms'].append(
+                        timeit(lambda: hand(x, skip), 20) * 1e3)
+                    entry['hand_unfused_ms'].append(
+                        timeit(lambda: hand(x) + skip, 20) * 1e3)
+        for key in ('unfused_ms', 'fused_ms', 'hand_unfused_ms'):
+            if key in entry:
+                best = min(entry[key])
+                entry[key.replace('_ms', '_tbps')] = nbytes / best / 1e9
+        res[f'up_{C}to{K}_{H}x{H}'] = entry
+        print(f'up_{C}to{K}_{H}x{H}', entry, flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, 'w') as f:
+        json.dump(res, f, indent=1)
+
+
+def probe_miopen_block(path, rounds=4):
+    from chunkflow_amd.fastconv import CfxMiopenResBlock
+
+    class ResBlock(nn.Module):
+        def __init__(self, c):
+            super().__init__()
+            self.conv1 = nn.Conv3d(c, c, 3, padding=1, bias=True)
+            self.conv2 = nn.Conv3d(c, c, 3, padding=1, bias=True)
+            self.act = nn.ELU(inplace=True)
+
+        def forward(self, x):
+            y = self.act(self.conv1(x))
+            y = self.conv2(y)
+            return self.act(x + y)
+
+    torch.manual_seed(0)
+    C, N, D, H = 48, 12, 20, 64
+    block = ResBlock(C).cuda().eval().to(memory_format=cl)
+    fused = CfxMiopenResBlock(block, 0).cuda()
+    x = torch.randn(N, C, D, H, H, device='cuda').contiguous(
+        memory_format=cl)
+    res = {'shape': [N, C, D, H, H], 'torch_ms': [], 'fused_ms': []}
+    with torch.no_grad():
+        res['max_err'] = (fused(x) - block(x)).abs().max().item()
+        for _ in range(rounds):
+            res['torch_ms'].append(timeit(lambda: block(x), 20) * 1e3)
+            res['fused_ms'].append(timeit(lambda: fused(x), 20) * 1e3)
+    res['fused_beats_torch_in_every_pair'] = all(
+        f < t for f, t in zip(res['fused_ms'], res['torch_ms']))
+    print(res, flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, 'w') as f:
+        json.dump(res, f, indent=1)
+
+
 def main():
+    if len(sys.argv) > 2 and sys.argv[1] == '--upskip':
+        probe_upskip(sys.argv[2])
+        return
+    if len(sys.argv) > 2 and sys.argv[1] == '--miopen-block':
+        probe_miopen_block(sys.argv[2])
+        return
     N, D = 12, 20  # config-2-like depth; config-5 uses N=24 D=32
     # RSUNet up/down shapes (H, W = input dims of the op)
     for bf16 in (True, False):
