@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -133,6 +134,19 @@ extern "C" int cfx_profile_get(cfx_ctx* ctx, int kernel_id,
 }
 
 // ---------------------------------------------------------------------------
+// vector-path alignment
+// ---------------------------------------------------------------------------
+// Every float4 (uchar4) path below reinterprets a base pointer plus offsets
+// that are multiples of 4 elements, so the base itself must sit on a 16-byte
+// (4-byte) boundary. Torch allocations always do; a view into one (t[1:])
+// need not, so each host-side `vec` decision checks the pointers as well as
+// the sizes and falls to the scalar kernel otherwise (the z-ring conv does
+// the same with `wvec`).
+static inline bool aligned_to(const void* p, uintptr_t bytes) {
+    return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0;
+}
+
+// ---------------------------------------------------------------------------
 // elementwise u8 -> f32 kernels (normalize-intensity, int->unit cast)
 // ---------------------------------------------------------------------------
 // out = (float)in * a + b; vectorized uchar4 -> float4. a/b are chosen by the
@@ -163,23 +177,27 @@ __global__ void k_u8_to_f32_tail(const unsigned char* __restrict__ in,
                                  float* __restrict__ out, long long start,
                                  long long n, float divisor, float bias) {
     long long i = start + blockIdx.x * (long long)blockDim.x + threadIdx.x;
-    if (i < n) out[i] = (float)in[i] / divisor + bias;
+    long long stride = gridDim.x * (long long)blockDim.x;
+    for (; i < n; i += stride) out[i] = (float)in[i] / divisor + bias;
 }
 
 static int u8_to_f32(cfx_ctx* ctx, const unsigned char* in, float* out,
                      long long n, float divisor, float bias, int kid) {
     hipEvent_t e0;
     if (prof_begin(ctx, &e0)) return -1;
-    long long n4 = n / 4;
+    int threads = 256;
+    // uchar4 -> float4 body only from a 4-byte source and 16-byte destination
+    long long n4 = aligned_to(in, 4) && aligned_to(out, 16) ? n / 4 : 0;
     if (n4 > 0) {
-        int threads = 256;
         long long want = (n4 + threads - 1) / threads;
         int blocks = (int)std::min<long long>(want, 8192);
         hipLaunchKernelGGL(k_u8_to_f32, dim3(blocks), dim3(threads), 0,
                            ctx->stream, in, out, n4, divisor, bias);
     }
-    if (n % 4) {
-        hipLaunchKernelGGL(k_u8_to_f32_tail, dim3(1), dim3(256), 0,
+    if (n4 * 4 < n) {
+        long long want = (n - n4 * 4 + threads - 1) / threads;
+        int blocks = (int)std::min<long long>(want, 8192);
+        hipLaunchKernelGGL(k_u8_to_f32_tail, dim3(blocks), dim3(threads), 0,
                            ctx->stream, in, out, n4 * 4, n, divisor, bias);
     }
     CFX_CHECK(hipGetLastError());
@@ -273,7 +291,9 @@ extern "C" int cfx_extract_patches(cfx_ctx* ctx, const float* chunk,
         int n = std::min(64, n_patches - base);
         ExtractArgs args;
         args.n = n;
-        bool vec = (W % 4 == 0) && (px % 4 == 0);
+        float* dst = out + (long long)base * channels * pvox;
+        bool vec = (W % 4 == 0) && (px % 4 == 0) && aligned_to(chunk, 16) &&
+                   aligned_to(dst, 16);
         for (int i = 0; i < n; ++i) {
             args.starts[i * 3 + 0] = starts_zyx[(base + i) * 3 + 0];
             args.starts[i * 3 + 1] = starts_zyx[(base + i) * 3 + 1];
@@ -285,7 +305,6 @@ extern "C" int cfx_extract_patches(cfx_ctx* ctx, const float* chunk,
         long long n_lines = (long long)n * channels * pz * py;
         long long n_groups = (n_lines + 1) / 2;  // G=2
         int blocks = (int)std::min<long long>((n_groups + 3) / 4, 8192);
-        float* dst = out + (long long)base * channels * pvox;
         if (vec)
             hipLaunchKernelGGL(k_extract<true>, dim3(blocks), dim3(64, 4),
                                0, ctx->stream, chunk, channels, D, H, W,
@@ -522,7 +541,9 @@ static int blend_one(cfx_ctx* ctx, float* out, int C, const int out_dims[3],
     int d0[3], p0[3], r[3];
     if (!clip_region(out_dims, patch_dims, offset, d0, p0, r)) return 0;
     bool vec = (out_dims[2] % 4 == 0) && (patch_dims[2] % 4 == 0) &&
-               (d0[2] % 4 == 0) && (p0[2] % 4 == 0) && (r[2] % 4 == 0);
+               (d0[2] % 4 == 0) && (p0[2] % 4 == 0) && (r[2] % 4 == 0) &&
+               aligned_to(out, 16) && aligned_to(patch, 16) &&
+               aligned_to(mask, 16);
     long long n_lines = (long long)C * r[0] * r[1];
     long long n_groups = (n_lines + 3) / 4;          // G=4 lines per group
     int blocks = (int)std::min<long long>((n_groups + 3) / 4, 8192);
@@ -568,7 +589,9 @@ extern "C" int cfx_blend_batch(cfx_ctx* ctx, float* out, int channels,
         BlendBatchArgs a;
         a.n = 0;
         a.line_start[0] = 0;
-        bool vec = (out_dims[2] % 4 == 0) && (patch_dims[2] % 4 == 0);
+        bool vec = (out_dims[2] % 4 == 0) && (patch_dims[2] % 4 == 0) &&
+                   aligned_to(out, 16) && aligned_to(patch, 16) &&
+                   aligned_to(mask, 16);
         int rxmax = 0;
         double bytes = 0.0;
         for (int i = 0; i < nb; ++i) {
@@ -677,8 +700,10 @@ extern "C" int cfx_build_chunk_mask(cfx_ctx* ctx, float* mask_out,
 // ---------------------------------------------------------------------------
 // mask-normalize multiply: out[c, i] *= mask[i]
 // ---------------------------------------------------------------------------
-// order-preserving bit transform lives below (f32_ord); forward-declare
+// order-preserving bit transforms live below; forward-declare
 __host__ __device__ inline unsigned int f32_ord(float f);
+__device__ inline unsigned int f32_max_ord(float wave_max, bool lane_nan);
+static float f32_max_decode(unsigned int ord);
 
 // mask-normalize: out[c, i] *= mask[i] for every channel, mask read ONCE
 // (channels in the inner loop — a per-channel grid re-reads the 0.54 GB
@@ -697,6 +722,7 @@ __global__ void k_maskmul(float* __restrict__ out,
     const float4* m4 = reinterpret_cast<const float4*>(mask);
     float4* o4 = reinterpret_cast<float4*>(out);
     float vmax = -INFINITY;
+    bool has_nan = false;  // fmaxf drops NaN; the scan must not (f32_max_ord)
     for (long long i = i0; i < n4; i += stride) {
         float4 mv[U];
         int nu = (int)(n4 - i < U ? n4 - i : U);
@@ -719,6 +745,10 @@ __global__ void k_maskmul(float* __restrict__ out,
                     if (WITHMAX) {
                         vmax = fmaxf(vmax, fmaxf(fmaxf(ov[u].x, ov[u].y),
                                                  fmaxf(ov[u].z, ov[u].w)));
+                        has_nan |= (ov[u].x != ov[u].x) |
+                                   (ov[u].y != ov[u].y) |
+                                   (ov[u].z != ov[u].z) |
+                                   (ov[u].w != ov[u].w);
                     }
                 }
             }
@@ -727,7 +757,8 @@ __global__ void k_maskmul(float* __restrict__ out,
     if (WITHMAX) {
         for (int off = 32; off > 0; off >>= 1)
             vmax = fmaxf(vmax, __shfl_down(vmax, off, 64));
-        if ((threadIdx.x & 63) == 0) atomicMax(result, f32_ord(vmax));
+        unsigned int ord = f32_max_ord(vmax, has_nan);
+        if ((threadIdx.x & 63) == 0) atomicMax(result, ord);
     }
 }
 
@@ -740,13 +771,20 @@ __global__ void k_maskmul_scalar(float* __restrict__ out,
         for (int c = 0; c < C; ++c) out[c * n + i] *= mask[i];
 }
 
+// float4 path (and with it the fused max) needs n_voxels % 4 == 0 and both
+// base pointers on 16 bytes
+static bool maskmul_vec(const float* out, const float* mask,
+                        long long n_voxels) {
+    return n_voxels % 4 == 0 && aligned_to(out, 16) && aligned_to(mask, 16);
+}
+
 static int multiply_mask_impl(cfx_ctx* ctx, float* out, const float* mask,
                               int channels, long long n_voxels,
                               bool with_max) {
     hipEvent_t e0;
     if (prof_begin(ctx, &e0)) return -1;
     int threads = 256;
-    if (n_voxels % 4 == 0) {
+    if (maskmul_vec(out, mask, n_voxels)) {
         long long n4 = n_voxels / 4;
         long long want = (n4 + threads * 2 - 1) / (threads * 2);
         int blocks = (int)std::min<long long>(want, 8192);
@@ -777,11 +815,12 @@ extern "C" int cfx_multiply_mask(cfx_ctx* ctx, float* out, const float* mask,
 }
 
 /* fused mask-normalize + max scan; returns -2 when the fused max is
- * unavailable (unaligned size) and the caller must cfx_max separately */
+ * unavailable (size or a pointer not float4-aligned) and the caller must
+ * cfx_max separately */
 extern "C" int cfx_multiply_mask_max(cfx_ctx* ctx, float* out,
                                      const float* mask, int channels,
                                      long long n_voxels, float* host_max) {
-    if (n_voxels % 4 != 0) {
+    if (!maskmul_vec(out, mask, n_voxels)) {
         int rc = multiply_mask_impl(ctx, out, mask, channels, n_voxels,
                                     false);
         return rc != 0 ? rc : -2;
@@ -795,10 +834,7 @@ extern "C" int cfx_multiply_mask_max(cfx_ctx* ctx, float* out,
     CFX_CHECK(hipMemcpyAsync(&outv, ctx->dev_max, sizeof(outv),
                              hipMemcpyDeviceToHost, ctx->stream));
     CFX_CHECK(hipStreamSynchronize(ctx->stream));
-    unsigned int u = (outv & 0x80000000u) ? (outv & 0x7fffffffu) : ~outv;
-    float f;
-    __builtin_memcpy(&f, &u, sizeof(f));
-    *host_max = f;
+    *host_max = f32_max_decode(outv);
     return 0;
 }
 
@@ -812,16 +848,49 @@ __host__ __device__ inline unsigned int f32_ord(float f) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
+// The scan exists for the reference's assert_array_less(out, 1.0001), which
+// raises on a NaN; fmaxf drops NaN and f32_ord sorts a negative one below
+// every number. So each lane also tracks "saw a NaN", and a wave that saw
+// one reports the top of the ordered domain, which wins the atomicMax and
+// decodes to NaN. NaN-free buffers take the f32_ord(fmaxf) path unchanged.
+// Call with the whole wave converged.
+#define CFX_ORD_NAN 0xffffffffu
+__device__ inline unsigned int f32_max_ord(float wave_max, bool lane_nan) {
+    return __any(lane_nan) ? CFX_ORD_NAN : f32_ord(wave_max);
+}
+
+static float f32_max_decode(unsigned int ord) {
+    unsigned int u = (ord & 0x80000000u) ? (ord & 0x7fffffffu) : ~ord;
+    if (ord == CFX_ORD_NAN) u = 0x7fc00000u;  // canonical quiet NaN
+    float f;
+    __builtin_memcpy(&f, &u, sizeof(f));
+    return f;
+}
+
 __global__ void k_max(const float* __restrict__ buf, long long n,
                       unsigned int* __restrict__ result) {
     long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
     long long stride = gridDim.x * (long long)blockDim.x;
     float m = -INFINITY;
-    for (; i < n; i += stride) m = fmaxf(m, buf[i]);
+    bool has_nan = false;
+    // four independent loads in flight per lane (the NaN test made the
+    // one-load loop issue-bound), then the remainder one by one
+    for (; i + 3 * stride < n; i += 4 * stride) {
+        float v0 = buf[i], v1 = buf[i + stride];
+        float v2 = buf[i + 2 * stride], v3 = buf[i + 3 * stride];
+        m = fmaxf(fmaxf(m, v0), fmaxf(fmaxf(v1, v2), v3));
+        has_nan |= (v0 != v0) | (v1 != v1) | (v2 != v2) | (v3 != v3);
+    }
+    for (; i < n; i += stride) {
+        float v = buf[i];
+        m = fmaxf(m, v);
+        has_nan |= v != v;
+    }
     // wave reduce (64 lanes), then one atomic per wave
     for (int off = 32; off > 0; off >>= 1)
         m = fmaxf(m, __shfl_down(m, off, 64));
-    if ((threadIdx.x & 63) == 0) atomicMax(result, f32_ord(m));
+    unsigned int ord = f32_max_ord(m, has_nan);
+    if ((threadIdx.x & 63) == 0) atomicMax(result, ord);
 }
 
 extern "C" int cfx_max(cfx_ctx* ctx, const float* buf, long long n,
@@ -842,8 +911,7 @@ extern "C" int cfx_max(cfx_ctx* ctx, const float* buf, long long n,
     CFX_CHECK(hipMemcpyAsync(&out, ctx->dev_max, sizeof(out),
                              hipMemcpyDeviceToHost, ctx->stream));
     CFX_CHECK(hipStreamSynchronize(ctx->stream));
-    unsigned int u = (out & 0x80000000u) ? (out & 0x7fffffffu) : ~out;
-    *host_max = __builtin_bit_cast(float, u);
+    *host_max = f32_max_decode(out);
     return 0;
 }
 
@@ -889,7 +957,8 @@ extern "C" int cfx_crop_margin(cfx_ctx* ctx, const float* in, float* out,
         g_err = "crop_margin: empty output";
         return -1;
     }
-    bool vec = (W % 4 == 0) && (oW % 4 == 0) && (margins[2] % 4 == 0);
+    bool vec = (W % 4 == 0) && (oW % 4 == 0) && (margins[2] % 4 == 0) &&
+               aligned_to(in, 16) && aligned_to(out, 16);
     long long n_lines = (long long)channels * oD * oH;
     int blocks = (int)std::min<long long>((n_lines + 3) / 4, 8192);
     hipEvent_t e0;

@@ -38,7 +38,9 @@ def _blend_reforder() -> bool:
     """Dispute-resolution switch: blend one patch per launch in the
     reference's exact order; default is the
     disjoint-group batching whose reordering is bounded by the ulp
-    argument in grouping.py. Read per call so tests can toggle it."""
+    argument in grouping.py. Covers the chunk-mask build as well as the
+    output blend, so the result is the oracle's bit for bit
+    (tests/test_stitch_exact.py). Read per call so tests can toggle it."""
     return os.environ.get('CFX_BLEND_REFORDER', '0') == '1'
 
 
@@ -283,10 +285,14 @@ class Inferencer:
         recip_mask = None
         if self.mask_output_chunk:
             # mask VALUES rebuilt per input chunk, like the reference
-            # (:294-333); the launch grouping is cached geometry
+            # (:294-333); the launch grouping is cached geometry. In
+            # reference-order mode the mask sum keeps the reference's order
+            # too (one launch per offset): a grouped mask differs in the
+            # last bit wherever three or more patches meet
             recip_mask = self.ops.build_chunk_mask(
                 out_size3, patch_mask_t, out_starts,
-                groups=self._groups(out_starts, out_size3))
+                groups=None if _blend_reforder()
+                else self._groups(out_starts, out_size3))
 
         if self.patch_shard is not None:
             shard_rank, shard_world = self.patch_shard

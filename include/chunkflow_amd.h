@@ -50,6 +50,14 @@ int cfx_make_patch_mask(const int patch_size[3], const int overlap[3],
                         float* out);
 
 /* ---- device kernels (all pointers are DEVICE pointers) ----------------- */
+/* Alignment contract: any element-aligned pointer is accepted. The float4
+ * (uchar4) fast paths of cfx_normalize_intensity / cfx_cast_u8_f32_div,
+ * cfx_extract_patches, cfx_blend_accumulate, cfx_blend_batch,
+ * cfx_multiply_mask(_max) and cfx_crop_margin are taken only when, besides
+ * the size and offset conditions, every f32 base pointer of the call is
+ * 16-byte aligned (the u8 source: 4-byte aligned); otherwise the scalar
+ * path computes the same bits. Allocations are always aligned; a view that
+ * starts at an odd element of one is not. */
 /* out[i] = (float)in[i] / 127.5f - 1.0f */
 int cfx_normalize_intensity(cfx_ctx* ctx, const unsigned char* in, float* out,
                             long long n);
@@ -87,11 +95,16 @@ int cfx_reciprocal(cfx_ctx* ctx, float* buf, long long n);
 /* out[c*n + i] *= mask[i] for every channel c (mask-normalize) */
 int cfx_multiply_mask(cfx_ctx* ctx, float* out, const float* mask,
                       int channels, long long n_voxels);
-/* synchronous max over n floats (the <1.0001 sanity assert) */
+/* synchronous max over n floats (the <1.0001 sanity assert). If the buffer
+ * holds a NaN of either sign at any position, *host_max is NaN, so that
+ * `max < 1.0001` fails as the reference's assert_array_less does; otherwise
+ * it is the largest element. */
 int cfx_max(cfx_ctx* ctx, const float* buf, long long n, float* host_max);
 /* fused mask-normalize + max scan (saves a full output read pass);
- * returns -2 when n_voxels is not float4-aligned — multiply done, call
- * cfx_max yourself */
+ * returns -2 when n_voxels is not a multiple of 4 or out / mask is not
+ * 16-byte aligned — multiply done, call cfx_max yourself. *host_max is the
+ * max of the PRODUCT and, like cfx_max, NaN whenever the product holds a
+ * NaN of either sign; the multiply itself is not affected. */
 int cfx_multiply_mask_max(cfx_ctx* ctx, float* out, const float* mask,
                           int channels, long long n_voxels,
                           float* host_max);
