@@ -9,7 +9,13 @@ raster-scan first-encounter order), which the GPU union-find reproduces
 exactly (min-index roots ranked in flat order; csrc/cc.hip).
 
 Device chunks run the gfx950 union-find; host chunks use scipy. With a
-threshold both implement the binary semantics (threshold > t). Without a
+threshold both implement the binary semantics (voxel > threshold), and the
+comparison is done in the chunk's own dtype on either path: an f16 voxel is
+compared with the threshold rounded to f16, an f64 voxel with the f64
+threshold, an integer voxel exactly (never through an f32 copy, which would
+move voxels within half an f32 ulp of the threshold across it); f32 chunks
+go through cfx_threshold, every other dtype builds its mask with a device
+comparison in that dtype. Without a
 threshold the reference's cc3d keeps EQUAL-VALUE semantics (each connected
 region of one value is one component; 0 is background). On the host that is
 `equal_value_label` (per-value scipy labeling renumbered in raster-scan
@@ -87,17 +93,29 @@ def connected_component_gpu(chunk: Chunk, threshold: float = None,
             labels.data_ptr(), scratch.data_ptr())
         return Chunk(labels, voxel_offset=chunk.voxel_offset,
                      voxel_size=chunk.voxel_size)
-    fg = torch.empty(dims, dtype=torch.uint8, device=t3.device)
-    if threshold is not None:
-        if t3.dtype != torch.float32:
-            t3 = t3.to(torch.float32)
+    if threshold is not None and t3.dtype == torch.float32:
+        fg = torch.empty(dims, dtype=torch.uint8, device=t3.device)
         ops.cfx.threshold(t3.data_ptr(), fg.data_ptr(), n, float(threshold))
+    elif threshold is not None:
+        fg = _threshold_in_own_dtype(t3, threshold)
     else:
         fg = (t3 != 0).to(torch.uint8).contiguous()
     ops.cfx.connected_components(fg.data_ptr(), dims, connectivity,
                                  labels.data_ptr(), scratch.data_ptr())
     return Chunk(labels, voxel_offset=chunk.voxel_offset,
                  voxel_size=chunk.voxel_size)
+
+
+def _threshold_in_own_dtype(t3, threshold):
+    """`t3 > threshold` as a u8 mask, evaluated as numpy evaluates it on the
+    host array of the same dtype: a float chunk compares in its own dtype
+    (the threshold is rounded to it), an integer chunk against a float
+    threshold compares in float64 (torch alone would round both sides to
+    float32, and 2**24 + 1 > 2.0**24 would be lost)."""
+    if isinstance(threshold, float) and not t3.is_floating_point():
+        threshold = torch.tensor(threshold, dtype=torch.float64,
+                                 device=t3.device)
+    return (t3 > threshold).to(torch.uint8).contiguous()
 
 
 def _is_label_dtype(t) -> bool:

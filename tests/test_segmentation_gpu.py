@@ -2,12 +2,16 @@
 equal-value connected components (A), per-label counts and masks (B), the
 error returns of the label-table entries (C) and the CLI chain with the
 chunk resident in HBM (D). Everything is integer: no tolerance anywhere."""
+import os
+import sys
 import warnings
 
 import numpy as np
 import pytest
 import torch
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from cc_cases import as_dtype  # noqa: E402  (the u8/u32/u64 label mappings)
 from chunkflow_amd.chunk import Chunk
 from chunkflow_amd.connected import connected_component, equal_value_label
 from chunkflow_amd.segmentation import (mask_except, mask_except_host,
@@ -73,17 +77,6 @@ def cc_volumes(shape):
     vols['serpentine'] = serpentine(shape)
     vols['binary'] = rng.integers(0, 2, size=shape)
     return vols
-
-
-def as_dtype(vol, dtype):
-    """Distinct small ints -> distinct labels of `dtype`; the uint64 labels
-    share their low 32 bits and differ only above bit 32."""
-    vol = vol.astype(np.uint64)
-    if dtype == np.uint8:
-        return (vol * np.uint64(31)).astype(np.uint8)
-    if dtype == np.uint32:
-        return (vol * np.uint64(2 ** 31 // 4)).astype(np.uint32)
-    return (vol << np.uint64(32)) + (vol != 0) * np.uint64(9)
 
 
 _CC_REF = {}
