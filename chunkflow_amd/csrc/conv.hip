@@ -6,7 +6,12 @@
 // pinned bit-exactly by tests/test_conv_exact.py):
 //   cfx_conv3_ndhwc        k_conv3 slab, C = 28/36/48/64
 //   cfx_conv3_ndhwc_w32    k_conv3_w32 (32x32x2), C = 28
-//   cfx_conv3_ndhwc_zring  k_conv3_zring_pl, C = 28 [111 TF] and 36;
+//   cfx_conv3_ndhwc_zring  k_conv3_zring_pl, C = 28 [111 TF] (one launch,
+//                          two 16-wide tiles, LDS 157.2 KB) and 36 [117
+//                          TF] (two launches: columns 0..15 + the 4x4x1
+//                          block tile 32..35, 155.5 KB, then 16..31,
+//                          140.0 KB); block columns are summed per
+//                          k-slice, then (s0+s2)+(s1+s3) across lanes;
 //                          k_conv3_zring_dw, C = 48 (37 TF, slower than
 //                          the slab; kept as the only C=48 ring route)
 //   cfx_conv3_ndhwc_bf16   k_conv3_zring_bf16_a, C = 28 [610-646 TF];
@@ -453,7 +458,8 @@ namespace {
 // (staged once, amortized over D planes — per-tap-group re-staging was
 // most of the per-z overhead), and the input slab is a 3-plane ring with
 // ONE ~20 KB plane staged per z. LDS: ring 3 x SY x SX x C (60.5 KB at
-// C=28, TY=8, TX=16) + weights 27 x NT x C x 16 (96.8 KB) = 157 KB.
+// C=28, TY=8, TX=16) + weights 27 x C x (16 NT + 4 NT4) (96.8 KB) =
+// 157 KB (per width: below).
 // Software-pipelined: the NEXT plane's global loads are issued into
 // registers first, the 18 taps that only touch the two already-resident
 // planes run while those loads are in flight, then the registers drain to
@@ -464,7 +470,30 @@ namespace {
 // residual loads | 9 taps | outputs finished in registers | stores back to
 // back — no wait ever sees a pending store (DESIGN.md §10-r2 item 8 has
 // what the assembly looked like before and what each part was worth).
-template <int C, int K, int TY, int TX, int NTK>
+//
+// A ragged output width (K = 36 against the 16-wide tile) rides on
+// NT4 BLOCK TILES of 4 columns, starting at column J4, computed by
+// v_mfma_f32_4x4x1_16b_f32 out of the same A fragment: the lane's
+// in[pos = lane & 15][c = 4 kk + (lane >> 4)] read as 16 blocks of 4 lanes
+// is block b = lane >> 2 = (position group b & 3, k-slice b >> 2), row
+// lane & 3; with B = w[c = 4 kk + (lane >> 4)][J4 + 4 t + (lane & 3)] one
+// instruction is a 16-position x 4-column x 4-channel product at a quarter
+// of a 16x16x4 and no zero column (layout and issue cost:
+// tools/mfma_layout_probe.py --f32-blocks, profiles/zring_blocks_probe
+// .json). Register i of lane l then holds the k-slice l >> 4 partial of
+// position 4 ((l >> 2) & 3) + i, column l & 3; once per z the four
+// k-slices are added as (s_q + s_q^2) + (s_q^1 + s_q^3) — the same value
+// in every lane, xor-32 then xor-16 — and lane l keeps row l >> 4, so four
+// consecutive lanes store the 16 contiguous bytes of one position. The
+// block wall [tap][t][c][4] sits behind the 16-wide wall; a wave's read
+// of it touches 16 consecutive floats.
+//   C=28: one launch, NT=2, NT4=0: wall 96.8 KB, ring 60.5 KB = 157.2 KB
+//         (NT=1 + NT4=3 at J4=16 fits in 145.2 KB and was slower: three
+//         block MFMAs cost 28-30 issue cycles against the 32 of the
+//         padded tile they replace, and bring three more LDS reads)
+//   C=36: launch A j0=0, NT=1 + NT4=1 at J4=32: wall 62.2 + 15.6 KB, ring
+//         77.8 KB = 155.5 KB; launch B j0=16, NT=1, NT4=0: 140.0 KB
+template <int C, int K, int TY, int TX, int NTK, int NT4, int J4>
 __global__ __launch_bounds__(512, 1) void k_conv3_zring_pl(
     const float* __restrict__ in, const float* __restrict__ wgt,
     const float* __restrict__ bias, const float* __restrict__ res,
@@ -475,17 +504,22 @@ __global__ __launch_bounds__(512, 1) void k_conv3_zring_pl(
     constexpr int SY = TY + 2;
     constexpr int KK = C / 4;
     constexpr int NT = NTK;
+    constexpr int N4 = NT4 > 0 ? NT4 : 1;  // array extent (unused at NT4=0)
     constexpr int NW = 8;
     constexpr int XT = TX / 16;
     constexpr int M_TILES = (TY * XT) / NW;
     constexpr int C4N = C / 4;
     constexpr int LV = (SY * SX * C4N + 511) / 512;  // loads held per thread
-    constexpr int WV4 = 27 * NT * C * 4;             // wall size in float4
+    constexpr int W16 = 27 * NT * C * 16;            // 16-wide wall, floats
+    constexpr int W16V4 = W16 / 4;
+    constexpr int WV4 = W16V4 + 27 * NT4 * C;        // wall size in float4
     constexpr int WL = (WV4 + 511) / 512;            // wall float4 per thread
+    constexpr bool SPLIT = NT == 1;  // 16-wide chain split by kk parity
     static_assert((TY * XT) % NW == 0, "");
+    static_assert(NT4 == 0 || (J4 % 4 == 0 && J4 + 4 * NT4 <= K), "");
 
     __shared__ __attribute__((aligned(16))) float ring[3 * SY * SX * PC];
-    __shared__ __attribute__((aligned(16))) float wall[27 * NT * C * 16];
+    __shared__ __attribute__((aligned(16))) float wall[WV4 * 4];
 
     const int n = blockIdx.z;
     const int y0 = blockIdx.y * TY;
@@ -507,11 +541,14 @@ __global__ __launch_bounds__(512, 1) void k_conv3_zring_pl(
 #pragma unroll
         for (int li = 0; li < WL; ++li) {
             const int idx = min(tid + li * 512, WV4 - 1);
-            const int row = idx >> 2;
+            // a float4 past the 16-wide wall is one whole (tap, t, c) row
+            // of a block tile, always below K
+            const bool blk = NT4 > 0 && idx >= W16V4;
+            const int row = blk ? idx - W16V4 : idx >> 2;
             const int c = row % C;
-            const int nt = row / C % NT;
-            const int tap = row / C / NT;
-            const int jg = j0 + nt * 16 + (idx & 3) * 4;
+            const int nt = blk ? row / C % N4 : row / C % NT;
+            const int tap = blk ? row / C / N4 : row / C / NT;
+            const int jg = blk ? J4 + nt * 4 : j0 + nt * 16 + (idx & 3) * 4;
             wk[li] = jg < K;
             wv[li] = *reinterpret_cast<const f32x4*>(
                 wgt + ((long long)tap * C + c) * K + (jg < K ? jg : 0));
@@ -527,7 +564,7 @@ __global__ __launch_bounds__(512, 1) void k_conv3_zring_pl(
         }
     };
     if (!wvec) {
-        for (int idx = tid; idx < 27 * NT * C * 16; idx += 512) {
+        for (int idx = tid; idx < W16; idx += 512) {
             const int j = idx & 15;
             const int c = (idx >> 4) % C;
             const int nt = (idx >> 4) / C % NT;
@@ -535,6 +572,13 @@ __global__ __launch_bounds__(512, 1) void k_conv3_zring_pl(
             const int jg = j0 + nt * 16 + j;
             wall[idx] =
                 jg < K ? wgt[((long long)tap * C + c) * K + jg] : 0.f;
+        }
+        for (int idx = tid; idx < 27 * NT4 * C * 4; idx += 512) {
+            const int c = (idx >> 2) % C;
+            const int t = (idx >> 2) / C % N4;
+            const int tap = (idx >> 2) / C / N4;
+            wall[W16 + idx] = wgt[((long long)tap * C + c) * K + J4 +
+                                  t * 4 + (idx & 3)];
         }
     }
 
@@ -621,23 +665,43 @@ __global__ __launch_bounds__(512, 1) void k_conv3_zring_pl(
 #pragma unroll
     for (int t = 0; t < NT; ++t)
         bj[t] = bias ? bias[min(j0 + t * 16 + colj, K - 1)] : 0.f;
+    // block tiles: the lane's B column, and the output it finishes —
+    // position pos4 of the m-tile, column J4 + 4 t + col4
+    const int col4 = lane & 3;
+    const int pos4 = ((lane >> 2) & 3) * 4 + (lane >> 4);
+    float bj4[N4];
+#pragma unroll
+    for (int t = 0; t < NT4; ++t)
+        bj4[t] = bias ? bias[J4 + t * 4 + col4] : 0.f;
+    // The lane's index into the block wall, hidden from the optimizer:
+    // folded into the 16-wide wall's address family, the block wall's
+    // 243 NT4 read addresses lie past the 64 KB reach of a ds_read offset
+    // from that base, and hipcc then keeps every one of them in a VGPR of
+    // its own across the z loop (194 spills at C=36). Opaque, they share
+    // one base register.
+    int w4lane = W16 + a_k * 4 + col4;
+    asm volatile("" : "+v"(w4lane));
 
     for (int z = 0; z < D; ++z) {
         // Two accumulator chains per m-tile: consecutive MFMAs on the
         // SAME accumulator pay the 40-cyc dependent latency against a
         // 32-cyc issue slot (PMC: 51.6% SQ_WAIT_INST_ANY with the naive
         // nt-outer order). kk-outer alternates the NT=2 accumulators
-        // (bit-identical sums — each chain keeps its order); NT==1
+        // (bit-identical sums — each chain keeps its order); SPLIT
         // splits by kk parity into acc/acc2 (a benign reassociation,
-        // folded in the epilogue).
+        // folded in the epilogue). Each block tile has its own chain.
         f32x4 acc[M_TILES][NT];
         f32x4 acc2[M_TILES];
+        f32x4 acc4[M_TILES][N4];
 #pragma unroll
         for (int m = 0; m < M_TILES; ++m) {
             acc2[m] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int t = 0; t < NT; ++t)
                 acc[m][t] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int t = 0; t < N4; ++t)
+                acc4[m][t] = {0.f, 0.f, 0.f, 0.f};
         }
 
         auto compute_dzi = [&](int dzi) {
@@ -656,6 +720,7 @@ __global__ __launch_bounds__(512, 1) void k_conv3_zring_pl(
                                      a_row * PC + a_k];
                 }
                 const float* wblk = &wall[tap * NT * C * 16];
+                const float* wblk4 = &wall[w4lane + tap * NT4 * C * 4];
 #pragma unroll
                 for (int kk = 0; kk < KK; ++kk) {
                     float a[M_TILES];
@@ -668,12 +733,30 @@ __global__ __launch_bounds__(512, 1) void k_conv3_zring_pl(
                             wblk[(nt * C + kk * 4 + a_k) * 16 + col16];
 #pragma unroll
                         for (int m = 0; m < M_TILES; ++m) {
-                            f32x4& dst = (NT == 1 && (kk & 1))
+                            f32x4& dst = (SPLIT && (kk & 1))
                                              ? acc2[m] : acc[m][nt];
                             dst = __builtin_amdgcn_mfma_f32_16x16x4f32(
                                 a[m], b, dst, 0, 0, 0);
                         }
                     }
+#pragma unroll
+                    for (int t = 0; t < NT4; ++t) {
+                        const float b4 =
+                            wblk4[(t * C + kk * 4) * 4];
+#pragma unroll
+                        for (int m = 0; m < M_TILES; ++m)
+                            acc4[m][t] = __builtin_amdgcn_mfma_f32_4x4x1f32(
+                                a[m], b4, acc4[m][t], 0, 0, 0);
+                    }
+                    // One scheduling group per step; LDS reads, VALU and
+                    // SALU may cross (mask 0x106). Without it hipcc
+                    // spills 8 VGPRs at C=36. In the first 18 taps each step's
+                    // MFMAs stay together; behind the barrier the C=36
+                    // launch still runs its 81 block MFMAs after the 81
+                    // 16-wide ones and holds their A values (255 VGPRs,
+                    // no spill, occupancy is 2 by LDS either way;
+                    // profiles/kernel_resources_zring_blocks.txt).
+                    if (NT4 > 0) __builtin_amdgcn_sched_barrier(0x106);
                 }
             }
         };
@@ -700,10 +783,17 @@ __global__ __launch_bounds__(512, 1) void k_conv3_zring_pl(
         // share the counter, so a wait behind a pending store is also a
         // wait for that store's acknowledgement.)
         float rv[M_TILES][NT][4];
+        float rv4[M_TILES][N4];
         if (res) {
 #pragma unroll
             for (int m = 0; m < M_TILES; ++m) {
                 const int gym = min(y0 + tmy[m], H - 1);
+                const int gx4 = min(x0 + tmx[m] + pos4, W - 1);
+#pragma unroll
+                for (int t = 0; t < NT4; ++t)
+                    rv4[m][t] = res[
+                        ((((long long)n * D + z) * H + gym) * W + gx4) * K +
+                        J4 + t * 4 + col4];
 #pragma unroll
                 for (int t = 0; t < NT; ++t) {
                     const int jm = min(j0 + t * 16 + colj, K - 1);
@@ -741,10 +831,44 @@ __global__ __launch_bounds__(512, 1) void k_conv3_zring_pl(
                 }
             }
         }
+        // Block tiles: every lane adds the four k-slices of all four rows
+        // in the one order (s_q + s_q^2) + (s_q^1 + s_q^3), keeps the row
+        // of its own k-slice index, then bias, residual, ELU as above.
+        float ov4[M_TILES][N4];
+#pragma unroll
+        for (int m = 0; m < M_TILES; ++m) {
+#pragma unroll
+            for (int t = 0; t < NT4; ++t) {
+                float v = 0.f;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    float s = acc4[m][t][i];
+                    s += __shfl_xor(s, 32);
+                    s += __shfl_xor(s, 16);
+                    v = a_k == i ? s : v;
+                }
+                v += bj4[t];
+                if (res) v += rv4[m][t];
+                if (do_elu) {
+                    const float e = expm1f(v > 0.f ? 0.f : v);
+                    v = v > 0.f ? v : e;
+                }
+                ov4[m][t] = v;
+            }
+        }
 #pragma unroll
         for (int m = 0; m < M_TILES; ++m) {
             const int gy = y0 + tmy[m];
             if (gy >= H) continue;
+            // four consecutive lanes write the 16 contiguous bytes of one
+            // position's block-tile columns
+            const int gx4 = x0 + tmx[m] + pos4;
+#pragma unroll
+            for (int t = 0; t < NT4; ++t) {
+                if (gx4 >= W) continue;
+                out[((((long long)n * D + z) * H + gy) * W + gx4) * K + J4 +
+                    t * 4 + col4] = ov4[m][t];
+            }
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
                 const int j = j0 + t * 16 + colj;
@@ -968,19 +1092,24 @@ extern "C" int cfx_conv3_ndhwc_zring(cfx_ctx* ctx, const float* in,
     const int wvec =
         (reinterpret_cast<uintptr_t>(wgt) % 16 == 0 && K % 4 == 0) ? 1 : 0;
     if (C == 28 && K == 28) {
-        // wall holds both K tiles (96.8 KB + 60.5 KB ring)
-        hipLaunchKernelGGL((k_conv3_zring_pl<28, 28, 8, 16, 2>), grid,
-                           dim3(512), 0, ctx->stream, in, wgt, bias,
+        // wall holds both K tiles (96.8 KB + 60.5 KB ring). Three block
+        // tiles for columns 16..27 instead of the second tile measured
+        // slower (6.37 -> 6.61 ms)
+        hipLaunchKernelGGL((k_conv3_zring_pl<28, 28, 8, 16, 2, 0, 0>),
+                           grid, dim3(512), 0, ctx->stream, in, wgt, bias,
                            residual, out, N, D, H, W, do_elu, 0, wvec);
     } else if (C == 36 && K == 36) {
-        // one 16-wide K tile per launch (wall 62.2 KB + ring 77.8 KB);
-        // the input re-read costs ~3x HBM traffic of a 113 MB activation
-        // per conv — negligible next to the compute
-        for (int j0 = 0; j0 < 36; j0 += 16) {
-            hipLaunchKernelGGL((k_conv3_zring_pl<36, 36, 8, 16, 1>), grid,
-                               dim3(512), 0, ctx->stream, in, wgt, bias,
-                               residual, out, N, D, H, W, do_elu, j0, wvec);
-        }
+        // the wall beside the ring holds one 16-wide K tile, so two
+        // launches: A = columns 0..15 plus 32..35 on a block tile out of
+        // the same staged planes, B = columns 16..31. The input re-read
+        // costs ~2x HBM traffic of a 113 MB activation per conv —
+        // negligible next to the compute
+        hipLaunchKernelGGL((k_conv3_zring_pl<36, 36, 8, 16, 1, 1, 32>),
+                           grid, dim3(512), 0, ctx->stream, in, wgt, bias,
+                           residual, out, N, D, H, W, do_elu, 0, wvec);
+        hipLaunchKernelGGL((k_conv3_zring_pl<36, 36, 8, 16, 1, 0, 0>),
+                           grid, dim3(512), 0, ctx->stream, in, wgt, bias,
+                           residual, out, N, D, H, W, do_elu, 16, wvec);
     } else if (C == 48 && K == 48) {
         // double-buffered per-dzi weight wall (full wall no longer fits
         // beside the ring); one 16-wide K tile per launch

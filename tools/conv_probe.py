@@ -87,11 +87,17 @@ def probe_zring(C, D, H, W, N=12, fused=False, iters=20, tag=''):
         passes.append((time.perf_counter() - t0) / iters * 1e3)
     ms = min(passes)
     flops = 2.0 * 27 * C * C * N * D * H * W
+    # per column group: the 16-wide MFMA tiles, then the 4-wide block tiles
+    groups = {28: [(0, 16), (16, 28)],
+              36: [(0, 16), (16, 32), (32, 36)]}.get(C, [(0, C)])
     print(json.dumps({
         'tag': tag, 'C': C, 'shape': [N, D, H, W], 'fused': fused,
         'ms': round(ms, 4), 'ms_passes': [round(p, 4) for p in passes],
         'TF': round(flops / ms / 1e9, 2),
-        'checksum': float(out.double().sum().item())}), flush=True)
+        'checksum': float(out.double().sum().item()),
+        'checksum_cols': {f'{a}..{b - 1}':
+                          float(out[:, a:b].double().sum().item())
+                          for a, b in groups}}), flush=True)
 
 
 if __name__ == '__main__' and '--zring-stalls' in sys.argv:
