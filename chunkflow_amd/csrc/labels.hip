@@ -1,7 +1,9 @@
-// Per-label voxel counts and label masking on gfx950: the device primitives
-// under chunkflow_amd/segmentation.py (unique_counts, mask_fragments,
-// mask_except — the reference's mask-out-objects operator, flow/flow.py
-// :2015-2050 + chunk/segmentation.py:86-109).
+// Per-label voxel counts, label masking and the contingency table of two
+// label volumes on gfx950: the device primitives under
+// chunkflow_amd/segmentation.py (unique_counts, mask_fragments, mask_except —
+// the reference's mask-out-objects operator, flow/flow.py:2015-2050 +
+// chunk/segmentation.py:86-109; contingency — its evaluate-segmentation
+// operator, flow/flow.py:1519-1542, see the pair count pass below).
 //
 // Label table: open addressing with linear probing in caller-owned HBM.
 //   keys  u64[capacity]  32-bit labels are zero-extended; all-ones = empty,
@@ -46,7 +48,7 @@ constexpr int SEG_BYTES = 64;  // per lane: half a 128-byte line
 constexpr unsigned long long EMPTY = ~0ull;
 constexpr int kCountGrid = 2048;  // 8 workgroups per CU on 256 CUs
 
-enum : unsigned int { ST_FULL = 1u, ST_RESERVED = 2u };
+enum : unsigned int { ST_FULL = 1u, ST_RESERVED = 2u, ST_MISSING = 4u };
 
 inline int grid_for(long long items) {
     long long want = (items + kBlock - 1) / kBlock;
@@ -295,6 +297,158 @@ __global__ void k_count(const T* __restrict__ in, long long begin,
 }
 
 // ---------------------------------------------------------------------------
+// pair count pass: the contingency table of two volumes walked in lockstep.
+// Both volumes were counted into tables of their own first, so every label
+// has a slot there; the key of a (seg, gt) pair is (slot_seg << 32) | slot_gt,
+// a u64 that goes through the same Table code as a label. Single tables are
+// at most 2^31 slots, so a pair key never has its top bit set and cannot
+// equal EMPTY. The single tables are read-only here: table_find is safe.
+//
+// One lane owns PSEG = SEG_BYTES / max(element size) voxels of each volume
+// and keeps a running (seg, gt, length): one table operation per run of equal
+// PAIRS, and a slot is looked up again only for the side that changed.
+// ---------------------------------------------------------------------------
+constexpr unsigned int NO_SLOT = 0xFFFFFFFFu;  // above any slot of a 2^31 table
+
+template <typename T, int N>
+struct alignas(sizeof(T) * N) Pack {
+    T e[N];
+};
+
+template <typename TS, typename TG>
+struct PairGeom {
+    static constexpr int WIDE =
+        (int)(sizeof(TS) > sizeof(TG) ? sizeof(TS) : sizeof(TG));
+    static constexpr int E = 16 / WIDE;          // voxels per load step
+    static constexpr int SEG = SEG_BYTES / WIDE;  // voxels per lane
+};
+
+// f(seg value, gt value) per voxel of the lane's segment, in order. VEC:
+// len == SEG and both pointers are aligned to their E-element load (16 bytes
+// for the wider type, 8 for a u32 stream beside a u64 one).
+template <typename TS, typename TG, bool VEC, typename F>
+__device__ inline void walk_pair_segment(const TS* __restrict__ ps,
+                                         const TG* __restrict__ pg, int len,
+                                         F&& f) {
+    constexpr int E = PairGeom<TS, TG>::E;
+    constexpr int SEG = PairGeom<TS, TG>::SEG;
+    if (VEC) {
+#pragma unroll 1
+        for (int c = 0; c < SEG / E; ++c) {
+            Pack<TS, E> a = *reinterpret_cast<const Pack<TS, E>*>(ps + c * E);
+            Pack<TG, E> b = *reinterpret_cast<const Pack<TG, E>*>(pg + c * E);
+#pragma unroll
+            for (int e = 0; e < E; ++e) f(a.e[e], b.e[e]);
+        }
+    } else {
+#pragma unroll 1
+        for (int j = 0; j < len; ++j) f(ps[j], pg[j]);
+    }
+}
+
+// slot of a label in its own (finished) table; NO_SLOT with a status flag
+// for the reserved label and for one the table does not hold
+__device__ inline unsigned int pair_slot(const Table& t,
+                                         unsigned long long key,
+                                         unsigned int* status) {
+    if (key == EMPTY) {
+        atomicOr(status, ST_RESERVED);
+        return NO_SLOT;
+    }
+    long long slot = table_find(t, key);
+    if (slot < 0) {
+        atomicOr(status, ST_MISSING);
+        return NO_SLOT;
+    }
+    return (unsigned int)slot;
+}
+
+__device__ inline void count_pair_lds(unsigned long long* lkeys,
+                                      unsigned int* lvals, const Table& t,
+                                      unsigned int ss, unsigned int sg,
+                                      unsigned int len,
+                                      unsigned int* status) {
+    if (ss == NO_SLOT || sg == NO_SLOT) return;  // already flagged
+    count_run_lds(lkeys, lvals, t, ((unsigned long long)ss << 32) | sg, len,
+                  status);
+}
+
+// same convergence argument as k_count
+template <typename TS, typename TG, bool VEC>
+__global__ void k_pair_count(const TS* __restrict__ seg,
+                             const TG* __restrict__ gt, long long begin,
+                             long long end, Table ts, Table tg, Table t,
+                             unsigned int* status) {
+    constexpr int SEG = PairGeom<TS, TG>::SEG;
+    __shared__ unsigned long long lkeys[LDS_SLOTS];
+    __shared__ unsigned int lvals[LDS_SLOTS];
+    for (int i = threadIdx.x; i < LDS_SLOTS; i += blockDim.x) {
+        lkeys[i] = EMPTY;
+        lvals[i] = 0u;
+    }
+    __syncthreads();
+    const long long n_items = (end - begin + SEG - 1) / SEG;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    const int lane = threadIdx.x & 63;
+    for (long long item0 = (long long)blockIdx.x * blockDim.x
+                           + (threadIdx.x - lane);
+         item0 < n_items; item0 += stride) {
+        const long long item = item0 + lane;
+        const bool active = item < n_items;
+        TS cs = TS(0);
+        TG cg = TG(0);
+        unsigned int ss = NO_SLOT, sg = NO_SLOT;
+        unsigned int runlen = 0, flushed = 0;
+        if (active) {
+            long long s = begin + item * SEG;
+            int len = (int)(end - s < SEG ? end - s : SEG);
+            walk_pair_segment<TS, TG, VEC>(
+                seg + s, gt + s, len, [&](TS vs, TG vg) {
+                    const bool first = runlen == 0;
+                    const bool ds = first || vs != cs;
+                    const bool dg = first || vg != cg;
+                    if (ds || dg) {
+                        if (!first) {
+                            count_pair_lds(lkeys, lvals, t, ss, sg, runlen,
+                                           status);
+                            ++flushed;
+                            runlen = 0;
+                        }
+                        if (ds) {
+                            cs = vs;
+                            ss = pair_slot(ts, (unsigned long long)vs,
+                                           status);
+                        }
+                        if (dg) {
+                            cg = vg;
+                            sg = pair_slot(tg, (unsigned long long)vg,
+                                           status);
+                        }
+                    }
+                    ++runlen;
+                });
+        }
+        // slots are one-to-one with labels: equal slot pairs, equal pairs
+        const unsigned long long key = ((unsigned long long)ss << 32) | sg;
+        const unsigned long long first = __shfl(key, 0, 64);
+        const bool uniform =
+            __all(!active || (flushed == 0 && key == first));
+        if (uniform) {
+            unsigned int sum = active ? runlen : 0u;
+            for (int off = 32; off > 0; off >>= 1)
+                sum += __shfl_down(sum, off, 64);
+            if (lane == 0 && active)
+                count_pair_lds(lkeys, lvals, t, ss, sg, sum, status);
+        } else if (active) {
+            count_pair_lds(lkeys, lvals, t, ss, sg, runlen, status);
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < LDS_SLOTS; i += blockDim.x)
+        if (lkeys[i] != EMPTY) count_run(t, lkeys[i], lvals[i], status);
+}
+
+// ---------------------------------------------------------------------------
 // apply pass: out = keep(label) ? label : 0, one lookup per run
 //   MODE 0 (fragments): keep iff the label's count exceeds `threshold`
 //   MODE 1 (except):    keep iff the label is in the table with a set flag
@@ -419,6 +573,12 @@ int read_status(cfx_ctx* ctx, unsigned long long* word, const char* who) {
                 + ": the label 2^64-1 is reserved (empty-slot key)";
         return -1;
     }
+    if (st & ST_MISSING) {
+        g_err = std::string(who)
+                + ": a label is missing from its table (count each volume "
+                  "into its table first)";
+        return -1;
+    }
     if (st & ST_FULL) {
         g_err = std::string(who)
                 + ": label table full (more distinct labels than capacity)";
@@ -473,6 +633,38 @@ int launch_count(cfx_ctx* ctx, const T* in, long long n, Table t,
     if (head + body < n)
         hipLaunchKernelGGL((k_count<T, false>), dim3(1), dim3(kBlock), 0,
                            ctx->stream, in, head + body, n, t, status);
+    CFX_CHECK(hipGetLastError());
+    return 0;
+}
+
+// the first h in [0, 4) at which seg + h and gt + h are both 16-byte aligned
+// starts the vector body; a pair of views with no such h is all scalar
+template <typename TS, typename TG>
+int launch_pair_count(cfx_ctx* ctx, const TS* seg, const TG* gt, long long n,
+                      Table ts, Table tg, Table t, unsigned int* status) {
+    constexpr int SEG = PairGeom<TS, TG>::SEG;
+    long long head = n, body = 0;
+    for (long long h = 0; h < 4; ++h)
+        if (misalign16(seg + h) == 0 && misalign16(gt + h) == 0) {
+            head = std::min(h, n);
+            body = (n - head) / SEG * SEG;
+            break;
+        }
+    if (head > 0)
+        hipLaunchKernelGGL((k_pair_count<TS, TG, false>),
+                           dim3(std::min(grid_for((head + SEG - 1) / SEG),
+                                         kCountGrid)),
+                           dim3(kBlock), 0, ctx->stream, seg, gt, 0ll, head,
+                           ts, tg, t, status);
+    if (body > 0)
+        hipLaunchKernelGGL((k_pair_count<TS, TG, true>),
+                           dim3(std::min(grid_for(body / SEG), kCountGrid)),
+                           dim3(kBlock), 0, ctx->stream, seg, gt, head,
+                           head + body, ts, tg, t, status);
+    if (head + body < n)
+        hipLaunchKernelGGL((k_pair_count<TS, TG, false>), dim3(1),
+                           dim3(kBlock), 0, ctx->stream, seg, gt,
+                           head + body, n, ts, tg, t, status);
     CFX_CHECK(hipGetLastError());
     return 0;
 }
@@ -586,6 +778,72 @@ extern "C" int cfx_label_count(cfx_ctx* ctx, const void* labels,
     if (rc) return rc;
     if (prof_end(ctx, e0, CFX_K_LABELS, (double)n * elem_bytes)) return -1;
     return read_status(ctx, words + 1, "label_count");
+}
+
+extern "C" int cfx_label_pair_count(
+    cfx_ctx* ctx, const void* seg, int seg_bytes, const int seg_dims[3],
+    const unsigned long long* seg_keys, long long seg_capacity,
+    const void* gt, int gt_bytes, const int gt_dims[3],
+    const unsigned long long* gt_keys, long long gt_capacity,
+    unsigned long long* keys, unsigned int* vals, long long capacity) {
+    const char* who = "label_pair_count";
+    long long n, n_gt;
+    if (check_volume(seg_dims, seg_bytes, who, &n)) return -1;
+    if (check_volume(gt_dims, gt_bytes, who, &n_gt)) return -1;
+    if (seg_dims[0] != gt_dims[0] || seg_dims[1] != gt_dims[1]
+        || seg_dims[2] != gt_dims[2]) {
+        g_err = std::string(who) + ": the two volumes differ in shape";
+        return -1;
+    }
+    if (!seg || !gt) {
+        g_err = std::string(who) + ": null volume";
+        return -1;
+    }
+    if (check_table(keys, vals, capacity, who)) return -1;
+    // only the keys of the single tables are read
+    if (check_table(seg_keys, seg_keys, seg_capacity, who)) return -1;
+    if (check_table(gt_keys, gt_keys, gt_capacity, who)) return -1;
+    if (seg_capacity > (1ll << 31) || gt_capacity > (1ll << 31)) {
+        g_err = std::string(who)
+                + ": a single table above 2^31 slots has no 31-bit slot index";
+        return -1;
+    }
+    unsigned long long* words;
+    if (status_words(ctx, &words)) return -1;
+    unsigned int* status = reinterpret_cast<unsigned int*>(words + 1);
+    hipEvent_t e0;
+    if (prof_begin(ctx, &e0)) return -1;
+    CFX_CHECK(hipMemsetAsync(words + 1, 0, sizeof(unsigned long long),
+                             ctx->stream));
+    Table ts{const_cast<unsigned long long*>(seg_keys), nullptr,
+             (unsigned long long)seg_capacity - 1};
+    Table tg{const_cast<unsigned long long*>(gt_keys), nullptr,
+             (unsigned long long)gt_capacity - 1};
+    Table t{keys, vals, (unsigned long long)capacity - 1};
+    typedef unsigned int u32;
+    typedef unsigned long long u64;
+    int rc;
+    if (seg_bytes == 4 && gt_bytes == 4)
+        rc = launch_pair_count(ctx, static_cast<const u32*>(seg),
+                               static_cast<const u32*>(gt), n, ts, tg, t,
+                               status);
+    else if (seg_bytes == 4)
+        rc = launch_pair_count(ctx, static_cast<const u32*>(seg),
+                               static_cast<const u64*>(gt), n, ts, tg, t,
+                               status);
+    else if (gt_bytes == 4)
+        rc = launch_pair_count(ctx, static_cast<const u64*>(seg),
+                               static_cast<const u32*>(gt), n, ts, tg, t,
+                               status);
+    else
+        rc = launch_pair_count(ctx, static_cast<const u64*>(seg),
+                               static_cast<const u64*>(gt), n, ts, tg, t,
+                               status);
+    if (rc) return rc;
+    if (prof_end(ctx, e0, CFX_K_LABELS,
+                 (double)n * (seg_bytes + gt_bytes)))
+        return -1;
+    return read_status(ctx, words + 1, who);
 }
 
 extern "C" int cfx_label_mask(cfx_ctx* ctx, const void* in, void* out,

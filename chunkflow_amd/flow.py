@@ -13,6 +13,8 @@ operators (reference chunkflow/flow/flow.py):
   connected-components  :1803-1829 (gfx950 union-find on device chunks)
   mask-out-objects      :2015-2050 (dust removal + object selection; gfx950
                                    label-table kernels on device chunks)
+  evaluate-segmentation :1519-1542 (scores against a ground truth; gfx950
+                                   contingency table on device chunks)
   normalize-contrast    :1672-1710 (device histogram/LUT kernels)
   load-h5 / save-h5     :976-1120  (in-repo HDF5 codec — h5io.py)
   load-tif / save-tif   :918-974   (in-repo TIFF codec — tiffio.py)
@@ -395,6 +397,35 @@ def mask_out_objects(tasks, input_chunk_name, output_chunk_name,
                 task[input_chunk_name],
                 dust_size_threshold=dust_size_threshold,
                 selected_obj_ids=selected_obj_ids)
+        yield task
+
+
+@main.command('evaluate-segmentation')
+@click.option('--segmentation-chunk-name', '-s', type=str, default='chunk',
+              help='chunk name of segmentation')
+@click.option('--groundtruth-chunk-name', '-g', type=str,
+              default='groundtruth')
+@click.option('--output', '-o', type=str, default='seg_score',
+              help='segmentation evaluation result name.')
+@operator
+def evaluate_segmentation(tasks, segmentation_chunk_name,
+                          groundtruth_chunk_name, output):
+    """Evaluate segmentation by split/merge error (device chunks stay on
+    the device: only the contingency table comes to the host)."""
+    from .segmentation import evaluate as _evaluate
+    for task in tasks:
+        if task is not None:
+            scores = _evaluate(task[segmentation_chunk_name],
+                               task[groundtruth_chunk_name])
+            print(f'rand index: {scores["rand_index"]: .3f}')
+            print('adjusted rand index: '
+                  f'{scores["adjusted_rand_index"]: .3f}')
+            print('variation of information: '
+                  f'{scores["variation_of_information"]: .3f}')
+            print(f'edit distance: {scores["edit_distance"]}')
+            print('Fowlkes Mallows Index: '
+                  f'{scores["fowlkes_mallows_index"]: .3f}')
+            task[output] = scores
         yield task
 
 

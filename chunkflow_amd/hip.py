@@ -25,7 +25,8 @@ SYMBOLS = [
     'cfx_mask_using_last_channel', 'cfx_threshold', 'cfx_nonzero_u8',
     'cfx_connected_components', 'cfx_connected_components_labels',
     'cfx_label_run_starts', 'cfx_label_table_clear',
-    'cfx_label_table_insert', 'cfx_label_count', 'cfx_label_mask',
+    'cfx_label_table_insert', 'cfx_label_count', 'cfx_label_pair_count',
+    'cfx_label_mask',
     'cfx_hist_u8', 'cfx_lut_apply_u8',
     'cfx_downsample_avg_u8', 'cfx_downsample_avg_f32',
     'cfx_downsample_mode2', 'cfx_downsample_mode3',
@@ -295,6 +296,19 @@ class CfxContext:
             ctypes.c_int(elem_bytes), _i3(dims), ctypes.c_void_p(keys_ptr),
             ctypes.c_void_p(vals_ptr), ctypes.c_longlong(capacity)),
             'cfx_label_count')
+
+    def label_pair_count(self, seg_ptr, seg_bytes, seg_dims, seg_keys_ptr,
+                         seg_capacity, gt_ptr, gt_bytes, gt_dims,
+                         gt_keys_ptr, gt_capacity, keys_ptr, vals_ptr,
+                         capacity):
+        self._chk(self.lib.cfx_label_pair_count(
+            ctypes.c_void_p(self.ctx), ctypes.c_void_p(seg_ptr),
+            ctypes.c_int(seg_bytes), _i3(seg_dims),
+            ctypes.c_void_p(seg_keys_ptr), ctypes.c_longlong(seg_capacity),
+            ctypes.c_void_p(gt_ptr), ctypes.c_int(gt_bytes), _i3(gt_dims),
+            ctypes.c_void_p(gt_keys_ptr), ctypes.c_longlong(gt_capacity),
+            ctypes.c_void_p(keys_ptr), ctypes.c_void_p(vals_ptr),
+            ctypes.c_longlong(capacity)), 'cfx_label_pair_count')
 
     def label_mask(self, in_ptr, out_ptr, elem_bytes, dims, keys_ptr,
                    vals_ptr, capacity, mode, threshold=0):

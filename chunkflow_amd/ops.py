@@ -240,6 +240,72 @@ class HipOps:
         return (ids[order].to(t.dtype),
                 counts[order].to(torch.int64) & 0xFFFFFFFF)
 
+    def label_pair_table(self, seg: torch.Tensor, gt: torch.Tensor,
+                         capacity: int = None):
+        """(seg_keys, gt_keys, keys, vals, info): the contingency table of
+        two contiguous int32/int64 volumes of equal shape. Each volume is
+        counted into a table of its own; a key of the pair table is
+        (slot in seg_keys << 32) | slot in gt_keys and its value the number
+        of voxels that carry that pair. `info` records the bounds and
+        capacities of the three tables.
+
+        Sizing. Call voxel i a pair run start if i == 0 or (seg[i], gt[i])
+        != (seg[i-1], gt[i-1]). The pair differs from its predecessor only
+        if seg or gt does, so every pair run start but voxel 0 is a run
+        start of seg or of gt, and voxel 0 is one of both:
+            pair run starts <= run_starts(seg) + run_starts(gt) - 1.
+        By the first-occurrence argument of label_count_table, applied to
+        the pairs as labels, distinct pairs <= pair run starts (and <= n).
+        The pair table is sized from that sum — both terms are already
+        known from sizing the single tables — and can never come out too
+        small. `capacity` overrides the sizing (a power of two; a table
+        that is too small makes the call raise "label table full")."""
+        if seg.shape != gt.shape:
+            raise ValueError(f'label_pair_table: shapes differ: '
+                             f'{tuple(seg.shape)} and {tuple(gt.shape)}')
+        dims = tuple(seg.shape)
+        seg_keys, _, seg_cap, seg_bound = self.label_count_table(seg)
+        gt_keys, _, gt_cap, gt_bound = self.label_count_table(gt)
+        bound = min(seg_bound + gt_bound - 1, seg.numel())
+        if capacity is None:
+            keys, vals, capacity = self._new_label_table(bound, seg.device)
+        else:
+            keys = torch.empty(capacity, dtype=torch.int64,
+                               device=seg.device)
+            vals = torch.empty(capacity, dtype=torch.int32,
+                               device=seg.device)
+            self.cfx.label_table_clear(keys.data_ptr(), vals.data_ptr(),
+                                       capacity)
+        self.cfx.label_pair_count(
+            seg.data_ptr(), seg.element_size(), dims, seg_keys.data_ptr(),
+            seg_cap, gt.data_ptr(), gt.element_size(), dims,
+            gt_keys.data_ptr(), gt_cap, keys.data_ptr(), vals.data_ptr(),
+            capacity)
+        info = {'seg_bound': seg_bound, 'seg_capacity': seg_cap,
+                'gt_bound': gt_bound, 'gt_capacity': gt_cap,
+                'pair_bound': bound, 'pair_capacity': capacity}
+        return seg_keys, gt_keys, keys, vals, info
+
+    def label_contingency(self, seg: torch.Tensor, gt: torch.Tensor):
+        """(seg_ids, gt_ids, counts), one row per distinct (seg, gt) pair,
+        sorted lexicographically by UNSIGNED (seg, gt). Ids are int64
+        carrying uint64 (32-bit labels zero-extended), counts int64."""
+        seg = self._check_labels(seg, 'label_contingency')
+        gt = self._check_labels(gt, 'label_contingency')
+        seg_keys, gt_keys, keys, vals, _ = self.label_pair_table(seg, gt)
+        used = keys != -1
+        pair, counts = keys[used], vals[used]
+        seg_ids = seg_keys[pair >> 32]
+        gt_ids = gt_keys[pair & 0xFFFFFFFF]
+        # the table is small: ordering it is torch plumbing. Two stable
+        # sorts, minor key first; the sign-bit flip gives unsigned order.
+        order = torch.argsort(torch.bitwise_xor(gt_ids, -2 ** 63),
+                              stable=True)
+        order = order[torch.argsort(
+            torch.bitwise_xor(seg_ids[order], -2 ** 63), stable=True)]
+        return (seg_ids[order], gt_ids[order],
+                counts[order].to(torch.int64) & 0xFFFFFFFF)
+
     def label_mask_fragments(self, t: torch.Tensor,
                              voxel_num_threshold: int) -> torch.Tensor:
         t = self._check_labels(t, 'label_mask_fragments')

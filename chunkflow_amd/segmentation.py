@@ -1,7 +1,9 @@
-"""Segmentation cleanup: per-label voxel counts, dust removal and object
-selection (PRODUCT code) — the reference's `mask-out-objects` operator
-(flow/flow.py:2015-2050) and the Segmentation methods under it
-(chunk/segmentation.py:86-109).
+"""Segmentation cleanup and scoring: per-label voxel counts, dust removal,
+object selection and evaluation against a ground truth (PRODUCT code).
+
+Cleanup is the reference's `mask-out-objects` operator (flow/flow.py
+:2015-2050) and the Segmentation methods under it (chunk/segmentation.py
+:86-109).
 
 The reference delegates to `fastremap.unique`, `fastremap.mask` and
 `fastremap.mask_except`. The pin here is to those functions' DOCUMENTED
@@ -27,6 +29,23 @@ labels) with byte-identical results. Device int32 / int64 tensors carry
 uint32 / uint64 labels, as in downsample: labels compare as raw bit
 patterns, `unique_counts` orders them by UNSIGNED value, and ids passed to
 `mask_except` are unsigned values.
+
+Evaluation — the reference's `evaluate-segmentation` operator (flow/flow.py
+:1519-1542 -> Segmentation.evaluate, chunk/segmentation.py:33-67 ->
+lib/gala/evaluate.py):
+
+  contingency(seg, gt)       (seg_ids, gt_ids, counts): one row per distinct
+                             (seg, gt) pair of labels with its voxel count,
+                             sorted by unsigned (seg, gt); zero is a label
+  scores_from_contingency    the five scores from those rows, on the host
+                             in float64
+  evaluate(seg, gt, t)       the reference's dict of scores
+
+Every score is a function of the contingency table alone, so the device
+path only has to build the table (csrc/labels.hip, k_pair_count); both
+paths then share scores_from_contingency, and equal tables give identical
+floats. The reference's quirks that are reproduced are listed at
+scores_from_contingency and in DESIGN.md.
 
 Out of contract on the device: the label 2^64-1 (the table's empty-slot
 key; the kernels report it as an error) and volumes of more than 2^32-1
@@ -184,3 +203,179 @@ def mask_out_objects(chunk: Chunk, dust_size_threshold: int = None,
     if selected_obj_ids is not None:
         chunk = mask_except(chunk, selected_obj_ids)
     return chunk
+
+
+# --- evaluation against a ground truth --------------------------------------
+SCORE_KEYS = ('rand_index', 'adjusted_rand_index', 'variation_of_information',
+              'fowlkes_mallows_index', 'edit_distance')
+
+
+def _as_u64(arr: np.ndarray) -> np.ndarray:
+    """astype(np.uint64) as the reference does (signed values wrap)."""
+    return np.ascontiguousarray(arr).astype(np.uint64, copy=False)
+
+
+def contingency_host(seg: np.ndarray, gt: np.ndarray):
+    """Runs of equal pairs in flat order first (the device kernel's view of
+    the volume), then a lexsort of the runs only."""
+    s, g = _as_u64(seg).ravel(), _as_u64(gt).ravel()
+    n = s.size
+    start = np.ones(n, dtype=bool)
+    start[1:] = (s[1:] != s[:-1]) | (g[1:] != g[:-1])
+    idx = np.flatnonzero(start)
+    lens = np.diff(np.append(idx, n)).astype(np.int64)
+    rs, rg = s[idx], g[idx]
+    order = np.lexsort((rg, rs))
+    rs, rg, lens = rs[order], rg[order], lens[order]
+    first = np.ones(rs.size, dtype=bool)
+    first[1:] = (rs[1:] != rs[:-1]) | (rg[1:] != rg[:-1])
+    fidx = np.flatnonzero(first)
+    return rs[fidx], rg[fidx], np.add.reduceat(lens, fidx)
+
+
+def _device_labels(chunk: Chunk, device):
+    """The chunk's labels as an int32/int64 tensor on `device`, carrying
+    uint32 / uint64: a host chunk is uploaded, a narrow dtype widened."""
+    if chunk.is_device:
+        t = chunk.array
+        if t.dtype not in (torch.int32, torch.int64):
+            t = t.to(torch.int64)
+        return t.to(device)
+    arr = np.ascontiguousarray(chunk.numpy().array)
+    if arr.dtype == np.uint32:
+        arr = arr.view(np.int32)
+    elif arr.dtype != np.int64:
+        arr = _as_u64(arr).view(np.int64)
+    return torch.from_numpy(arr).to(device)
+
+
+def contingency(seg: Chunk, gt: Chunk):
+    """(seg_ids, gt_ids, counts): for every pair of labels (s, g) that some
+    voxel carries, the number of voxels that do; rows sorted by unsigned
+    (s, g), zero an ordinary label. Host chunks give numpy arrays (ids
+    uint64, counts int64). If either chunk is on the device the other is
+    uploaded and the gfx950 kernels build the table: device tensors, ids
+    int64 carrying uint64, counts int64. Only the arrays are compared: the
+    shapes must agree, the voxel offsets are not looked at (the reference
+    passes the arrays alone)."""
+    _check(seg, 'contingency')
+    _check(gt, 'contingency')
+    if tuple(seg.shape) != tuple(gt.shape):
+        raise ValueError(f'contingency: segmentation {tuple(seg.shape)} and '
+                         f'ground truth {tuple(gt.shape)} differ in shape')
+    if seg.is_device or gt.is_device:
+        anchor = seg if seg.is_device else gt
+        device = anchor.array.device
+        return _ops_for(anchor).label_contingency(
+            _device_labels(seg, device), _device_labels(gt, device))
+    return contingency_host(seg.numpy().array, gt.numpy().array)
+
+
+def _host_u64(ids) -> np.ndarray:
+    if torch is not None and isinstance(ids, torch.Tensor):
+        ids = ids.cpu().numpy()
+    ids = np.asarray(ids)
+    if ids.dtype == np.int64:
+        return ids.view(np.uint64)
+    return ids.astype(np.uint64)
+
+
+def _totals(ids: np.ndarray, counts: np.ndarray):
+    """(distinct ids, index of each row's id among them, exact totals)."""
+    uniq, inverse = np.unique(ids, return_inverse=True)
+    totals = np.zeros(uniq.size, dtype=np.uint64)
+    np.add.at(totals, inverse, counts)
+    return uniq, inverse, totals
+
+
+def _xlogx(x: np.ndarray) -> np.ndarray:
+    y = x.copy()
+    nz = y.nonzero()
+    y[nz] *= np.log2(y[nz])
+    return y
+
+
+def scores_from_contingency(seg_ids, gt_ids, counts,
+                            size_threshold: int = 1000) -> dict:
+    """The reference's scores (lib/gala/evaluate.py) from contingency rows,
+    on the host in float64; device triples are copied to the host first.
+    Returns the five keys of `evaluate` plus `false_splits_by_column`.
+
+    Rand, adjusted Rand and Fowlkes-Mallows use every voxel, zero being a
+    label like any other (the reference passes no ignore list there). The
+    four sums they need are exact integers (N < 2^32, so all fit a uint64);
+    they are converted to float64 once and closed with the reference's
+    expressions in its order of operations (evaluate.py:1215-1300), on
+    np.float64 so that 0/0 is NaN rather than an exception.
+
+    Variation of information uses only pairs with s != 0 and g != 0,
+    normalised by their total: H(gt|seg) + H(seg|gt) in log2; NaN when
+    there is no such pair, as in the reference.
+
+    edit_distance is (false_merges, 0.0). Of the pairs with s != 0, g != 0
+    and more than size_threshold voxels, false_merges = (number of such
+    pairs) - (number of distinct non-zero seg labels): a segment with no
+    surviving overlap contributes -1, so the value can be negative — the
+    reference's arithmetic. The second element is always 0.0: the reference
+    slices a 1 x N np.matrix with [1:], which empties it. The count it
+    meant, pairs - distinct non-zero gt labels, is `false_splits_by_column`.
+    """
+    s, g = _host_u64(seg_ids), _host_u64(gt_ids)
+    if torch is not None and isinstance(counts, torch.Tensor):
+        counts = counts.cpu().numpy()
+    n = np.asarray(counts).astype(np.uint64)
+    seg_uniq, seg_inv, seg_tot = _totals(s, n)
+    gt_uniq, gt_inv, gt_tot = _totals(g, n)
+    f64 = np.float64
+    with np.errstate(divide='ignore', invalid='ignore'):
+        total = f64(int(n.sum()))
+        sum1 = f64(int((n * n).sum()))
+        sum2 = f64(int((seg_tot * seg_tot).sum()))
+        sum3 = f64(int((gt_tot * gt_tot).sum()))
+        a = (sum1 - total) / 2.0
+        b = (sum2 - sum1) / 2
+        c = (sum3 - sum1) / 2
+        d = (sum1 + total ** 2 - sum2 - sum3) / 2
+        rand_index = (a + d) / (a + b + c + d)
+        nk = a + b + c + d
+        chance = (a + b) * (a + c) + (c + d) * (b + d)
+        adjusted_rand_index = (nk * (a + d) - chance) / (nk ** 2 - chance)
+        fowlkes_mallows_index = a / (np.sqrt((a + b) * (a + c)))
+
+        inner = (s != 0) & (g != 0)
+        m = n[inner].astype(f64)
+        if m.size == 0 or m.sum() == 0:
+            vi = f64('nan')
+        else:
+            pxy = m / m.sum()
+            si, gi = seg_inv[inner], gt_inv[inner]
+            px = np.bincount(si, weights=pxy, minlength=seg_uniq.size)
+            py = np.bincount(gi, weights=pxy, minlength=gt_uniq.size)
+            lpygx = np.bincount(si, weights=_xlogx(pxy / px[si]),
+                                minlength=seg_uniq.size)
+            lpxgy = np.bincount(gi, weights=_xlogx(pxy / py[gi]),
+                                minlength=gt_uniq.size)
+            hygx = -(px * lpygx)
+            hxgy = -(py * lpxgy)
+            vi = np.dot(np.ones(2), np.array([hygx.sum(), hxgy.sum()]))
+
+    survivors = int((inner & (n.astype(np.int64) > size_threshold)).sum())
+    false_merges = f64(survivors - int((seg_uniq != 0).sum()))
+    false_splits = f64(survivors - int((gt_uniq != 0).sum()))
+    return {
+        'rand_index': rand_index,
+        'adjusted_rand_index': adjusted_rand_index,
+        'variation_of_information': f64(vi),
+        'fowlkes_mallows_index': fowlkes_mallows_index,
+        'edit_distance': (false_merges, f64(0.0)),
+        'false_splits_by_column': false_splits,
+    }
+
+
+def evaluate(seg: Chunk, gt: Chunk, size_threshold: int = 1000) -> dict:
+    """Score a segmentation against a ground truth: the reference's
+    Segmentation.evaluate, with exactly its keys. Device chunks are scored
+    from a contingency table built on the device."""
+    scores = scores_from_contingency(*contingency(seg, gt),
+                                     size_threshold=size_threshold)
+    return {key: scores[key] for key in SCORE_KEYS}

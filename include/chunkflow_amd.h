@@ -173,6 +173,27 @@ int cfx_label_table_insert(cfx_ctx* ctx, const unsigned long long* ids,
 int cfx_label_count(cfx_ctx* ctx, const void* labels, int elem_bytes,
                     const int dims[3], unsigned long long* keys,
                     unsigned int* vals, long long capacity);
+/* The contingency table of two (D, H, W) volumes of equal shape, each of 4-
+ * or 8-byte labels (all four combinations): for every pair (s, g) that
+ * occurs at some voxel, vals[slot(key)] += the number of such voxels, on a
+ * cleared table. seg_keys / gt_keys are the key arrays of the tables that
+ * cfx_label_count filled from the same two volumes (their values are not
+ * read); the key of a pair is (slot of s in seg_keys << 32) | slot of g in
+ * gt_keys, so single tables above 2^31 slots are refused and a pair key
+ * never equals the empty marker. Counts are exact; zero is an ordinary
+ * label. The number of distinct pairs is at most run_starts(seg) +
+ * run_starts(gt) - 1: size the pair table from that. Errors: "label table
+ * full", the reserved label 2^64-1, a label that its single table does not
+ * hold, volumes that differ in shape. Synchronous (reads the status flags
+ * back). */
+int cfx_label_pair_count(cfx_ctx* ctx, const void* seg, int seg_bytes,
+                         const int seg_dims[3],
+                         const unsigned long long* seg_keys,
+                         long long seg_capacity, const void* gt, int gt_bytes,
+                         const int gt_dims[3],
+                         const unsigned long long* gt_keys,
+                         long long gt_capacity, unsigned long long* keys,
+                         unsigned int* vals, long long capacity);
 /* out[i] = keep(in[i]) ? in[i] : 0, zero staying zero. mode 0: keep iff the
  * label's value in the table is > threshold (dust removal over a counted
  * table); mode 1: keep iff the label is in the table with a non-zero value
@@ -307,7 +328,7 @@ enum cfx_kernel_id {
     CFX_K_CC = 9,
     CFX_K_CONV = 10,
     CFX_K_CONV_STREAM = 11,  /* up/down-sample + (1,5,5) stream convs */
-    CFX_K_LABELS = 12,       /* label run-start / count / mask passes */
+    CFX_K_LABELS = 12,       /* label run-start / count / pair / mask passes */
     CFX_K_COUNT = 13
 };
 int cfx_profile_enable(cfx_ctx* ctx, int enable);
