@@ -51,36 +51,17 @@ class PyTorchEngine(EngineBase):
                               os.environ.get('CFX_CHANNELS_LAST', '1') != '0')
         if self.channels_last:
             self.model = self.model.to(memory_format=torch.channels_last_3d)
-            # swap eligible 3x3x3 ResBlock convs for the hand-written MFMA
-            # kernels (fastconv.py); CFX_FASTCONV=0 keeps MIOpen everywhere
+            # swap the ResBlock, up-, input and output convs for the
+            # hand-written kernels and fuse the decoder's skip-adds
+            # (fastconv.py); CFX_FASTCONV=0 keeps MIOpen everywhere
             if os.environ.get('CFX_FASTCONV', '1') != '0':
-                idx = int(str(self.device).split(':')[-1])                     if ':' in str(self.device) else 0
-                from ..fastconv import (accelerate_conv_in,
-                                        accelerate_updown)
-                bf = self.dtype == 'bfloat16'
-                if bf:
-                    from ..fastconv import maybe_accelerate_bf16
-                    self.fastconv_count = maybe_accelerate_bf16(
-                        self.model, idx)
-                else:
-                    from ..fastconv import maybe_accelerate
-                    self.fastconv_count = maybe_accelerate(self.model, idx)
-                self.fastconv_count += accelerate_updown(
-                    self.model, idx, bf16=bf)
-                self.fastconv_count += accelerate_conv_in(
-                    self.model, idx, bf16=bf)
-                # conv_out kernel beats MIOpen at both dtypes (13.6x bf16,
-                # 5.2x f32 -- profiles/convout_mfma.json)
-                from ..fastconv import accelerate_conv_out
-                self.fastconv_count += accelerate_conv_out(
-                    self.model, idx, bf16=bf)
-                # the decoder's `up(x) + skip` adds move into the up-conv's
-                # epilogue (torch.fx rewrite, f32 only; guarded)
-                self.upskip_count = 0
-                if not bf:
-                    from ..fastconv import accelerate_up_skip
-                    self.model, self.upskip_count = accelerate_up_skip(
-                        self.model, idx, self.num_input_channels)
+                from ..fastconv import accelerate_all
+                dev = str(self.device)
+                idx = int(dev.split(':')[-1]) if ':' in dev else 0
+                self.model, self.fastconv_count, self.upskip_count = \
+                    accelerate_all(self.model, idx,
+                                   self.dtype == 'bfloat16',
+                                   self.num_input_channels)
         torch.backends.cudnn.benchmark = True
         self.pre_process = getattr(net_source, 'pre_process', None)
         self.post_process = getattr(net_source, 'post_process', None)

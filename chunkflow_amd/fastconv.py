@@ -7,18 +7,25 @@ convs, ~85% of the affinity UNet's FLOPs. Everything else stays on
 MIOpen. Enabled in the pytorch engine via CFX_FASTCONV (see engine);
 weights are repacked once to the kernel's (27, C, K) tap-major layout.
 
-Further down: the up/down-sampling and (1,5,5) conv swaps
-(csrc/updown.hip), the torch.fx pass that moves the decoder's
-`up(x) + skip` add into the up-conv's epilogue (fuse_up_skip_adds), and
+Also here: the up/down-sampling and (1,5,5) conv swaps (csrc/updown.hip),
 CfxMiopenResBlock, which gives the ResBlocks whose convs stay on MIOpen a
-one-pass bias / residual / ELU epilogue.
+one-pass bias / residual / ELU epilogue, and the torch.fx pass that moves
+the decoder's `up(x) + skip` add into the up-conv's epilogue
+(fuse_up_skip_adds).
+
+The surgery itself is one walker (_walk) over a table of rules (_groups):
+a rule names which modules it takes, what replaces them and the input on
+which the replacement has to reproduce the original (_probe) before it is
+installed. accelerate_all runs every group in the engine's order.
 """
 import os
+from collections import namedtuple
 
 import torch
 import torch.nn as nn
 
 _CTX = {}
+_CL = torch.channels_last_3d
 
 
 def get_cfx(device_index: int = 0):
@@ -30,6 +37,47 @@ def get_cfx(device_index: int = 0):
     return _CTX[device_index]
 
 
+def _ptr(t):
+    """device address of an optional tensor (None is the C-ABI's NULL)"""
+    return None if t is None else t.data_ptr()
+
+
+def _empty_cl(x, shape, dtype):
+    return torch.empty(shape, dtype=dtype, device=x.device,
+                       memory_format=_CL)
+
+
+class _CfxModule(nn.Module):
+    """Base of every replacement module: the surgery never matches one."""
+
+    def _bias_buffer(self, conv, name='bias'):
+        b = conv.bias
+        self.register_buffer(
+            name, None if b is None else b.detach().float().contiguous())
+
+
+class _CfxConv(_CfxModule):
+    """Base of the single-conv drop-ins: widths, context index, dtype."""
+
+    def __init__(self, conv, device_index, bf16):
+        super().__init__()
+        self.C, self.K = conv.in_channels, conv.out_channels
+        self.device_index = device_index
+        self.bf16 = bf16
+        self.dt = torch.bfloat16 if bf16 else torch.float32
+
+    def _in(self, x):
+        """x channels-last, checked to be of the module's dtype, and its
+        n, d, h, w"""
+        assert x.dtype == self.dt, f'{type(self).__name__} runs {self.dt}'
+        x = x.contiguous(memory_format=_CL)
+        n, _, d, h, w = x.shape
+        return x, n, d, h, w
+
+
+# --------------------------------------------------------------------------
+# eligibility
+# --------------------------------------------------------------------------
 # widths where the hand kernel BEATS MIOpen (the persistent-z ring:
 # C=28 88.6 vs 81.9 TF, C=36 69.5 vs 64.7; 48/64 stay on MIOpen — the
 # weight wall no longer fits LDS beside the ring at those widths, and
@@ -37,89 +85,172 @@ def get_cfx(device_index: int = 0):
 ELIGIBLE_WIDTHS = (28, 36)
 ZRING_WIDTHS = (28, 36)
 
+# bf16 ring widths on the hand kernels (measured,
+# profiles/updown_probe_r02.json): C=28 594-624 TF (4x MIOpen), C=36
+# sliced 249 TF (1.31x). C=48 sliced reaches 318 vs MIOpen's 344 raw and
+# even with the fused ResBlock epilogue the same-box bench A/B reads
+# 292.4/293.5 (C48 on) vs 297.1/296.5 (off) MV/s -- measured-rejected,
+# kernel kept callable behind CFX_BF16_WIDTHS=28,36,48.
+BF16_WIDTHS = tuple(
+    int(w) for w in os.environ.get('CFX_BF16_WIDTHS', '28,36').split(',')
+    if w)
 
-def _eligible(m: nn.Module) -> bool:
-    return (isinstance(m, nn.Conv3d)
-            and m.kernel_size == (3, 3, 3)
-            and m.stride == (1, 1, 1)
-            and m.padding == (1, 1, 1)
+# up-conv surgery allowlist. bf16 (measured, profiles/updown_probe_r02.json):
+# the hand up-conv wins at in_channels 36 (7.1x) and ties at 48; it loses
+# at 64 (32^2 extent). f32 (profiles/upskip_probe.json, 12 x 20 patches, up
+# + skip-add): the MFMA up-conv with the add in its epilogue takes 0.73 ms
+# at 36 (5.6 TB/s; VALU kernel + torch add 2.0 ms), 0.26 ms at 48 (0.86)
+# and 0.09 ms at 64, where MIOpen + bias pass + add took 0.31 -- all three
+# levels are on. The down shapes lose to MIOpen everywhere (0.03-0.25x)
+# and keep it: no rule swaps them; CfxDownConv3d stays callable and
+# GPU-tested for the record.
+UP_SURGERY_WIDTHS = (36, 48)
+UP_SURGERY_WIDTHS_F32 = (36, 48, 64)
+
+
+def _is_conv(m, cls, kernel, stride, padding) -> bool:
+    """The one shape predicate: a plain (undilated, ungrouped) conv of
+    class `cls` with this kernel, stride and padding."""
+    return (isinstance(m, cls)
+            and m.kernel_size == kernel
+            and m.stride == stride
+            and m.padding == padding
             and m.dilation == (1, 1, 1)
             and m.groups == 1
+            and m.output_padding == (0, 0, 0))
+
+
+def _conv333(m, widths=None) -> bool:
+    return (_is_conv(m, nn.Conv3d, (3, 3, 3), (1, 1, 1), (1, 1, 1))
             and m.in_channels == m.out_channels
-            and m.in_channels in ELIGIBLE_WIDTHS)
+            and (widths is None or m.in_channels in widths))
 
 
-class CfxConv3d(nn.Module):
+def _eligible(m: nn.Module) -> bool:
+    return _conv333(m, ELIGIBLE_WIDTHS)
+
+
+def _eligible_bf16(m: nn.Module) -> bool:
+    return _conv333(m, BF16_WIDTHS)
+
+
+def _block_like(m: nn.Module, conv_ok) -> bool:
+    """The RSUNet ResBlock's attributes: conv1, conv2 (both `conv_ok`) and
+    an ELU(alpha=1) `act`. Whether the forward is the ResBlock's too is the
+    probe's business."""
+    return (hasattr(m, 'conv1') and hasattr(m, 'conv2')
+            and isinstance(getattr(m, 'act', None), nn.ELU)
+            and getattr(m.act, 'alpha', None) == 1.0
+            and not isinstance(m, _CfxModule)
+            and conv_ok(m.conv1) and conv_ok(m.conv2))
+
+
+def _resblock_like(m: nn.Module) -> bool:
+    return _block_like(m, _eligible)
+
+
+def _miopen_resblock_like(m: nn.Module) -> bool:
+    return (_block_like(m, lambda c: _conv333(c) and not _eligible(c))
+            and m.conv1.in_channels == m.conv2.in_channels)
+
+
+def _up_eligible(m, bf16: bool = False) -> bool:
+    widths = UP_SURGERY_WIDTHS if bf16 else UP_SURGERY_WIDTHS_F32
+    return (_is_conv(m, nn.ConvTranspose3d, (1, 2, 2), (1, 2, 2), (0, 0, 0))
+            and m.in_channels in widths
+            and m.out_channels <= 64)
+
+
+def _conv155(m) -> bool:
+    return _is_conv(m, nn.Conv3d, (1, 5, 5), (1, 1, 1), (0, 2, 2))
+
+
+def _conv155_eligible(m) -> bool:
+    return _conv155(m) and m.in_channels == 1 and m.out_channels <= 32
+
+
+def _conv155_out_eligible(m) -> bool:
+    return _conv155(m) and m.in_channels == 28 and m.out_channels == 3
+
+
+# --------------------------------------------------------------------------
+# 3x3x3 ResBlock convs
+# --------------------------------------------------------------------------
+class CfxConv3d(_CfxConv):
     """Drop-in for an eligible nn.Conv3d; consumes/produces channels-last
     (NDHWC) tensors, exactly the memory format the engine runs in."""
 
     def __init__(self, conv: nn.Conv3d, device_index: int = 0):
-        super().__init__()
-        self.C = conv.in_channels
-        self.K = conv.out_channels
-        self.device_index = device_index
+        super().__init__(conv, device_index, False)
         w = conv.weight.detach()  # (K, C, 3, 3, 3)
         wtap = w.permute(2, 3, 4, 1, 0).reshape(27, self.C, self.K)
         self.register_buffer('wtap', wtap.contiguous().float())
-        if conv.bias is not None:
-            self.register_buffer('bias', conv.bias.detach().float())
-        else:
-            self.bias = None
+        self._bias_buffer(conv)
 
     def _run(self, x, residual=None, elu=False):
-        x = x.contiguous(memory_format=torch.channels_last_3d)
-        n, c, d, h, w = x.shape
-        out = torch.empty((n, self.K, d, h, w), dtype=torch.float32,
-                          device=x.device,
-                          memory_format=torch.channels_last_3d)
+        x, n, d, h, w = self._in(x)
+        out = _empty_cl(x, (n, self.K, d, h, w), self.dt)
         get_cfx(self.device_index).conv3_ndhwc(
-            x.data_ptr(), self.wtap.data_ptr(),
-            self.bias.data_ptr() if self.bias is not None else None,
-            residual.data_ptr() if residual is not None else None,
-            out.data_ptr(), n, d, h, w, self.C, self.K, do_elu=elu,
-            zring=self.C in ZRING_WIDTHS)
+            x.data_ptr(), self.wtap.data_ptr(), _ptr(self.bias),
+            _ptr(residual), out.data_ptr(), n, d, h, w, self.C, self.K,
+            do_elu=elu, zring=self.C in ZRING_WIDTHS)
         return out
 
-    def forward(self, x):
-        assert x.dtype == torch.float32, 'fastconv is the f32 path'
-        return self._run(x)
+    forward = _run
 
 
-class CfxResBlock(nn.Module):
+class CfxConv3dBF16(_CfxConv):
+    """bf16 drop-in for an eligible nn.Conv3d (config-5 path): the bf16
+    persistent-z ring kernel on v_mfma_f32_32x32x16_bf16."""
+
+    def __init__(self, conv: nn.Conv3d, device_index: int = 0):
+        super().__init__(conv, device_index, True)
+        w = conv.weight.detach().float()  # (K, C, 3, 3, 3)
+        # C <= 32 uses the (27, 32, 32) pack of the single-tile ring;
+        # 36/48 use the (27, 64, 48) pack of the sliced 4-launch schedule
+        if self.C <= 32:
+            pack = torch.zeros(27, 32, 32)
+        else:
+            pack = torch.zeros(27, 64, 48)
+        pack[:, :self.K, :self.C] = w.permute(2, 3, 4, 0, 1) \
+            .reshape(27, self.K, self.C)
+        self.register_buffer('wpack', pack.to(torch.bfloat16).contiguous())
+        self._bias_buffer(conv)
+
+    def _run(self, x, residual=None, elu=False):
+        x, n, d, h, w = self._in(x)
+        out = _empty_cl(x, (n, self.K, d, h, w), self.dt)
+        get_cfx(self.device_index).conv3_ndhwc_bf16(
+            x.data_ptr(), self.wpack.data_ptr(), _ptr(self.bias),
+            _ptr(residual), out.data_ptr(), n, d, h, w, self.C, self.K,
+            do_elu=elu)
+        return out
+
+    forward = _run
+
+
+class CfxResBlock(_CfxModule):
     """Fused replacement for the RSUNet ResBlock pattern (conv1 -> ELU ->
     conv2 -> +x -> ELU): the ELU and residual-add run in the conv
     epilogues, removing three full-tensor elementwise passes per block."""
+    conv_cls = CfxConv3d
 
     def __init__(self, block: nn.Module, device_index: int = 0):
         super().__init__()
-        self.c1 = CfxConv3d(block.conv1, device_index)
-        self.c2 = CfxConv3d(block.conv2, device_index)
+        self.c1 = self.conv_cls(block.conv1, device_index)
+        self.c2 = self.conv_cls(block.conv2, device_index)
 
     def forward(self, x):
-        x = x.contiguous(memory_format=torch.channels_last_3d)
+        x = x.contiguous(memory_format=_CL)
         h = self.c1._run(x, elu=True)
         return self.c2._run(h, residual=x, elu=True)
 
 
-def _resblock_like(m: nn.Module) -> bool:
-    return (hasattr(m, 'conv1') and hasattr(m, 'conv2')
-            and isinstance(getattr(m, 'act', None), nn.ELU)
-            and getattr(m.act, 'alpha', None) == 1.0
-            and not isinstance(m, (CfxConv3d, CfxResBlock))
-            and _eligible(m.conv1) and _eligible(m.conv2))
+class CfxResBlockBF16(CfxResBlock):
+    conv_cls = CfxConv3dBF16
 
 
-def _conv333(m: nn.Module) -> bool:
-    return (isinstance(m, nn.Conv3d)
-            and m.kernel_size == (3, 3, 3)
-            and m.stride == (1, 1, 1)
-            and m.padding == (1, 1, 1)
-            and m.dilation == (1, 1, 1)
-            and m.groups == 1
-            and m.in_channels == m.out_channels)
-
-
-class CfxMiopenResBlock(nn.Module):
+class CfxMiopenResBlock(_CfxModule):
     """The RSUNet ResBlock pattern at the widths whose 3x3x3 convs stay on
     MIOpen (not in ELIGIBLE_WIDTHS): the convs run without bias, so torch
     launches no bias pass, and one in-place stream kernel per conv
@@ -133,207 +264,22 @@ class CfxMiopenResBlock(nn.Module):
         self.device_index = device_index
         for i, conv in ((1, block.conv1), (2, block.conv2)):
             self.register_buffer(f'w{i}', conv.weight.detach())
-            self.register_buffer(
-                f'b{i}', conv.bias.detach().float().contiguous()
-                if conv.bias is not None else None)
+            self._bias_buffer(conv, f'b{i}')
 
     def _conv(self, x, w, b, res):
         y = torch.nn.functional.conv3d(x, w, None, padding=1)
-        y = y.contiguous(memory_format=torch.channels_last_3d)
+        y = y.contiguous(memory_format=_CL)
         n, k, d, h, wd = y.shape
         get_cfx(self.device_index).bias_res_elu(
-            y.data_ptr(), b.data_ptr() if b is not None else None,
-            res.data_ptr() if res is not None else None,
-            n * d * h * wd, k, do_elu=True)
+            y.data_ptr(), _ptr(b), _ptr(res), n * d * h * wd, k,
+            do_elu=True)
         return y
 
     def forward(self, x):
         assert x.dtype == torch.float32, 'fastconv is the f32 path'
-        x = x.contiguous(memory_format=torch.channels_last_3d)
+        x = x.contiguous(memory_format=_CL)
         h = self._conv(x, self.w1, self.b1, None)
         return self._conv(h, self.w2, self.b2, x)
-
-
-def _miopen_resblock_like(m: nn.Module) -> bool:
-    return (hasattr(m, 'conv1') and hasattr(m, 'conv2')
-            and isinstance(getattr(m, 'act', None), nn.ELU)
-            and getattr(m.act, 'alpha', None) == 1.0
-            and not isinstance(m, (CfxConv3d, CfxResBlock,
-                                   CfxMiopenResBlock))
-            and _conv333(m.conv1) and _conv333(m.conv2)
-            and m.conv1.in_channels == m.conv2.in_channels
-            and not _eligible(m.conv1) and not _eligible(m.conv2))
-
-
-@torch.no_grad()
-def _fusion_matches(block: nn.Module, fused: nn.Module) -> bool:
-    """Functional probe at surgery time: the fused block must reproduce the
-    original forward on a random input (guards against user modules that
-    merely LOOK like a ResBlock)."""
-    if isinstance(fused, CfxMiopenResBlock):
-        C, dev = fused.C, fused.w1.device
-    else:
-        C, dev = fused.c1.C, fused.c1.wtap.device
-    x = torch.randn(1, C, 4, 18, 22, device=dev) \
-        .contiguous(memory_format=torch.channels_last_3d)
-    want = block.to(x.device)(x)
-    got = fused(x)
-    return bool(torch.allclose(got, want, rtol=1e-4, atol=1e-4))
-
-
-def maybe_accelerate(model: nn.Module, device_index: int = 0) -> int:
-    """Replace eligible ResBlocks (fused) and lone convs in-place;
-    returns the replacement count."""
-    count = 0
-    dev = f'cuda:{device_index}'
-    fused_out = set()  # detached originals (their convs must not re-count)
-    for parent in list(model.modules()):  # snapshot: we mutate the tree
-        if id(parent) in fused_out:
-            continue
-        for name, child in list(parent.named_children()):
-            if _resblock_like(child):
-                fused = CfxResBlock(child, device_index).to(dev)
-                if _fusion_matches(child, fused):
-                    setattr(parent, name, fused)
-                    fused_out.add(id(child))
-                    count += 1
-                    continue
-                # forward does something else: fall through to lone convs
-                for cn in ('conv1', 'conv2'):
-                    setattr(child, cn,
-                            CfxConv3d(getattr(child, cn),
-                                      device_index).to(dev))
-                    count += 1
-            elif _miopen_resblock_like(child):
-                fused = CfxMiopenResBlock(child, device_index).to(dev)
-                if _fusion_matches(child, fused):
-                    setattr(parent, name, fused)
-                    fused_out.add(id(child))
-                    count += 1
-            elif _eligible(child):
-                setattr(parent, name,
-                        CfxConv3d(child, device_index).to(dev))
-                count += 1
-    return count
-
-
-# bf16 ring widths on the hand kernels (measured,
-# profiles/updown_probe_r02.json): C=28 594-624 TF (4x MIOpen), C=36
-# sliced 249 TF (1.31x). C=48 sliced reaches 318 vs MIOpen's 344 raw and
-# even with the fused ResBlock epilogue the same-box bench A/B reads
-# 292.4/293.5 (C48 on) vs 297.1/296.5 (off) MV/s -- measured-rejected,
-# kernel kept callable behind CFX_BF16_WIDTHS=28,36,48.
-BF16_WIDTHS = tuple(
-    int(w) for w in os.environ.get('CFX_BF16_WIDTHS', '28,36').split(',')
-    if w)
-
-
-class CfxConv3dBF16(nn.Module):
-    """bf16 drop-in for an eligible nn.Conv3d (config-5 path): the bf16
-    persistent-z ring kernel on v_mfma_f32_32x32x16_bf16."""
-
-    def __init__(self, conv: nn.Conv3d, device_index: int = 0):
-        super().__init__()
-        self.C = conv.in_channels
-        self.K = conv.out_channels
-        self.device_index = device_index
-        w = conv.weight.detach().float()  # (K, C, 3, 3, 3)
-        # C <= 32 uses the (27, 32, 32) pack of the single-tile ring;
-        # 36/48 use the (27, 64, 48) pack of the sliced 4-launch schedule
-        if self.C <= 32:
-            pack = torch.zeros(27, 32, 32)
-        else:
-            pack = torch.zeros(27, 64, 48)
-        pack[:, :self.K, :self.C] = w.permute(2, 3, 4, 0, 1) \
-            .reshape(27, self.K, self.C)
-        self.register_buffer('wpack', pack.to(torch.bfloat16).contiguous())
-        if conv.bias is not None:
-            self.register_buffer('bias', conv.bias.detach().float())
-        else:
-            self.bias = None
-
-    def _run(self, x, residual=None, elu=False):
-        assert x.dtype == torch.bfloat16
-        x = x.contiguous(memory_format=torch.channels_last_3d)
-        n, c, d, h, w = x.shape
-        out = torch.empty((n, self.K, d, h, w), dtype=torch.bfloat16,
-                          device=x.device,
-                          memory_format=torch.channels_last_3d)
-        get_cfx(self.device_index).conv3_ndhwc_bf16(
-            x.data_ptr(), self.wpack.data_ptr(),
-            self.bias.data_ptr() if self.bias is not None else None,
-            residual.data_ptr() if residual is not None else None,
-            out.data_ptr(), n, d, h, w, self.C, self.K, do_elu=elu)
-        return out
-
-    def forward(self, x):
-        return self._run(x)
-
-
-class CfxResBlockBF16(nn.Module):
-    def __init__(self, block: nn.Module, device_index: int = 0):
-        super().__init__()
-        self.c1 = CfxConv3dBF16(block.conv1, device_index)
-        self.c2 = CfxConv3dBF16(block.conv2, device_index)
-
-    def forward(self, x):
-        x = x.contiguous(memory_format=torch.channels_last_3d)
-        h = self.c1._run(x, elu=True)
-        return self.c2._run(h, residual=x, elu=True)
-
-
-def maybe_accelerate_bf16(model: nn.Module, device_index: int = 0) -> int:
-    """bf16 surgery (widths where the bf16 ring is instantiated); same
-    functional-probe guard as the f32 path."""
-    count = 0
-    dev = f'cuda:{device_index}'
-
-    def elig(m):
-        return (isinstance(m, nn.Conv3d) and m.kernel_size == (3, 3, 3)
-                and m.stride == (1, 1, 1) and m.padding == (1, 1, 1)
-                and m.dilation == (1, 1, 1) and m.groups == 1
-                and m.in_channels == m.out_channels
-                and m.in_channels in BF16_WIDTHS)
-
-    def rb(m):
-        return (hasattr(m, 'conv1') and hasattr(m, 'conv2')
-                and isinstance(getattr(m, 'act', None), nn.ELU)
-                and getattr(m.act, 'alpha', None) == 1.0
-                and not isinstance(m, (CfxConv3dBF16, CfxResBlockBF16))
-                and elig(m.conv1) and elig(m.conv2))
-
-    @torch.no_grad()
-    def matches(block, fused):
-        x = torch.randn(1, fused.c1.C, 4, 18, 22, device=dev) \
-            .to(torch.bfloat16) \
-            .contiguous(memory_format=torch.channels_last_3d)
-        want = block.to(dev)(x)
-        got = fused(x)
-        return bool(torch.allclose(got.float(), want.float(), rtol=0.05,
-                                   atol=0.05))
-
-    fused_out = set()
-    for parent in list(model.modules()):  # snapshot: we mutate the tree
-        if id(parent) in fused_out:
-            continue
-        for name, child in list(parent.named_children()):
-            if rb(child):
-                fused = CfxResBlockBF16(child, device_index).to(dev)
-                if matches(child, fused):
-                    setattr(parent, name, fused)
-                    fused_out.add(id(child))
-                    count += 1
-                    continue
-                for cn in ('conv1', 'conv2'):
-                    setattr(child, cn,
-                            CfxConv3dBF16(getattr(child, cn),
-                                          device_index).to(dev))
-                    count += 1
-            elif elig(child):
-                setattr(parent, name,
-                        CfxConv3dBF16(child, device_index).to(dev))
-                count += 1
-    return count
 
 
 # --------------------------------------------------------------------------
@@ -341,24 +287,16 @@ def maybe_accelerate_bf16(model: nn.Module, device_index: int = 0) -> int:
 # are HBM-streaming work; csrc/updown.hip replaces MIOpen's implicit GEMM
 # (bf16 bwd_data runs ~20x below the stream roofline there).
 # --------------------------------------------------------------------------
-class CfxUpConv3d(nn.Module):
+class CfxUpConv3d(_CfxConv):
     """Drop-in for nn.ConvTranspose3d(kernel=(1,2,2), stride=(1,2,2))."""
 
     def __init__(self, conv: nn.ConvTranspose3d, device_index: int = 0,
                  bf16: bool = False):
-        super().__init__()
-        self.C = conv.in_channels
-        self.K = conv.out_channels
-        self.device_index = device_index
-        self.bf16 = bf16
+        super().__init__(conv, device_index, bf16)
         w = conv.weight.detach().float()      # (C, K, 1, 2, 2)
         pack = w[:, :, 0].permute(2, 3, 0, 1).reshape(4, self.C, self.K)
-        dt = torch.bfloat16 if bf16 else torch.float32
-        self.register_buffer('wpack', pack.to(dt).contiguous())
-        if conv.bias is not None:
-            self.register_buffer('bias', conv.bias.detach().float())
-        else:
-            self.bias = None
+        self.register_buffer('wpack', pack.to(self.dt).contiguous())
+        self._bias_buffer(conv)
 
     def _fusable(self, skip, out_shape) -> bool:
         """The kernel adds `skip` in its epilogue when it is what the
@@ -368,8 +306,7 @@ class CfxUpConv3d(nn.Module):
                 and skip.dtype == torch.float32
                 and skip.device == self.wpack.device
                 and tuple(skip.shape) == tuple(out_shape)
-                and skip.is_contiguous(
-                    memory_format=torch.channels_last_3d)
+                and skip.is_contiguous(memory_format=_CL)
                 and skip.data_ptr() % 16 == 0
                 and self.C % 4 == 0 and self.K % 4 == 0
                 and self.C <= 64 and self.K <= 48)
@@ -377,18 +314,12 @@ class CfxUpConv3d(nn.Module):
     def forward(self, x, skip=None):
         """up(x), or up(x) + skip. The sum is bit-identical either way:
         fused, the add is the kernel's last f32 operation."""
-        x = x.contiguous(memory_format=torch.channels_last_3d)
-        n, c, d, h, w = x.shape
-        dt = torch.bfloat16 if self.bf16 else torch.float32
-        assert x.dtype == dt
-        out = torch.empty((n, self.K, d, 2 * h, 2 * w), dtype=dt,
-                          device=x.device,
-                          memory_format=torch.channels_last_3d)
+        x, n, d, h, w = self._in(x)
+        out = _empty_cl(x, (n, self.K, d, 2 * h, 2 * w), self.dt)
         fuse = (skip is not None and self._fusable(skip, out.shape)
                 and x.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0)
         get_cfx(self.device_index).upconv_2x2_add(
-            x.data_ptr(), self.wpack.data_ptr(),
-            self.bias.data_ptr() if self.bias is not None else None,
+            x.data_ptr(), self.wpack.data_ptr(), _ptr(self.bias),
             skip.data_ptr() if fuse else None,
             out.data_ptr(), n, d, h, w, self.C, self.K, bf16=self.bf16)
         if skip is not None and not fuse:
@@ -396,96 +327,212 @@ class CfxUpConv3d(nn.Module):
         return out
 
 
-class CfxDownConv3d(nn.Module):
+class CfxDownConv3d(_CfxConv):
     """Drop-in for nn.Conv3d(kernel=(1,2,2), stride=(1,2,2))."""
 
     def __init__(self, conv: nn.Conv3d, device_index: int = 0,
                  bf16: bool = False):
-        super().__init__()
-        self.C = conv.in_channels
-        self.K = conv.out_channels
-        self.device_index = device_index
-        self.bf16 = bf16
+        super().__init__(conv, device_index, bf16)
         w = conv.weight.detach().float()      # (K, C, 1, 2, 2)
         pack = w[:, :, 0].permute(2, 3, 1, 0).reshape(4, self.C, self.K)
-        dt = torch.bfloat16 if bf16 else torch.float32
-        self.register_buffer('wpack', pack.to(dt).contiguous())
-        if conv.bias is not None:
-            self.register_buffer('bias', conv.bias.detach().float())
-        else:
-            self.bias = None
+        self.register_buffer('wpack', pack.to(self.dt).contiguous())
+        self._bias_buffer(conv)
 
     def forward(self, x):
-        x = x.contiguous(memory_format=torch.channels_last_3d)
-        n, c, d, h, w = x.shape
-        dt = torch.bfloat16 if self.bf16 else torch.float32
-        assert x.dtype == dt
-        out = torch.empty((n, self.K, d, h // 2, w // 2), dtype=dt,
-                          device=x.device,
-                          memory_format=torch.channels_last_3d)
+        x, n, d, h, w = self._in(x)
+        out = _empty_cl(x, (n, self.K, d, h // 2, w // 2), self.dt)
         get_cfx(self.device_index).downconv_2x2(
-            x.data_ptr(), self.wpack.data_ptr(),
-            self.bias.data_ptr() if self.bias is not None else None,
+            x.data_ptr(), self.wpack.data_ptr(), _ptr(self.bias),
             out.data_ptr(), n, d, h, w, self.C, self.K, bf16=self.bf16)
         return out
 
 
-# surgery allowlist. bf16 (measured, profiles/updown_probe_r02.json): the
-# hand up-conv wins at in_channels 36 (7.1x) and ties at 48; it loses at 64
-# (32^2 extent). f32 (profiles/upskip_probe.json, 12 x 20 patches, up +
-# skip-add): the MFMA up-conv with the add in its epilogue takes 0.73 ms
-# at 36 (5.6 TB/s; VALU kernel + torch add 2.0 ms), 0.26 ms at 48 (0.86)
-# and 0.09 ms at 64, where MIOpen + bias pass + add took 0.31 -- all three
-# levels are on. The down shapes lose to MIOpen everywhere (0.03-0.25x)
-# and keep it; kernels stay callable and GPU-tested for the record.
-UP_SURGERY_WIDTHS = (36, 48)
-UP_SURGERY_WIDTHS_F32 = (36, 48, 64)
+# --------------------------------------------------------------------------
+# the (1,5,5) input and output convs
+# --------------------------------------------------------------------------
+class CfxConvIn155(_CfxConv):
+    """Drop-in for nn.Conv3d(1, K, (1,5,5), padding=(0,2,2)) — the RSUNet
+    input conv. MIOpen's implicit GEMM degenerates on the single input
+    channel (measured 38.8 ms bf16 / 6.8 ms f32 per batch-24 launch vs
+    ~0.5 ms algorithmic); csrc/updown.hip runs it as a 2-D stencil."""
+
+    def __init__(self, conv: nn.Conv3d, device_index: int = 0,
+                 bf16: bool = False):
+        super().__init__(conv, device_index, bf16)
+        w = conv.weight.detach().float()      # (K, 1, 1, 5, 5)
+        self.register_buffer(
+            'wpack', w.reshape(self.K, 25).to(self.dt).contiguous())
+        self._bias_buffer(conv)
+
+    def forward(self, x):
+        assert x.shape[1] == 1
+        x, n, d, h, w = self._in(x)
+        out = _empty_cl(x, (n, self.K, d, h, w), self.dt)
+        get_cfx(self.device_index).conv155_c1(
+            x.data_ptr(), self.wpack.data_ptr(), _ptr(self.bias),
+            out.data_ptr(), n, d, h, w, self.K, bf16=self.bf16)
+        return out
 
 
-def _up_eligible(m, bf16: bool = False) -> bool:
-    widths = UP_SURGERY_WIDTHS if bf16 else UP_SURGERY_WIDTHS_F32
-    return (isinstance(m, nn.ConvTranspose3d)
-            and m.kernel_size == (1, 2, 2) and m.stride == (1, 2, 2)
-            and m.padding == (0, 0, 0) and m.output_padding == (0, 0, 0)
-            and m.dilation == (1, 1, 1) and m.groups == 1
-            and m.in_channels in widths
-            and m.out_channels <= 64)
+class CfxConvOut155(_CfxConv):
+    """Drop-in for nn.Conv3d(28, 3, (1,5,5), padding=(0,2,2)) — the
+    RSUNet output conv. MIOpen's bf16 implicit GEMM degenerates on the
+    tiny K (measured 38.6 ms per batch-24 launch vs 2.85 ms here;
+    f32 at batch 12 x 20: 6.76 ms vs 1.29 ms, profiles/convout_mfma.json).
+    28 -> 3 only: the five x-taps are folded into the MFMA's output
+    dimension (csrc/updown.hip)."""
+
+    def __init__(self, conv: nn.Conv3d, device_index: int = 0,
+                 bf16: bool = False):
+        super().__init__(conv, device_index, bf16)
+        assert (self.C, self.K) == (28, 3), 'conv_out kernel is 28 -> 3'
+        w = conv.weight.detach().float()      # (K, C, 1, 5, 5)
+        if bf16:                              # the kernel multiplies in f32
+            w = w.to(torch.bfloat16).float()
+        # B fragments of the 35 K-steps: [dy*7 + c//4][(c%4)*16 + j] with
+        # j = dx*3 + k and a zero 16th column
+        pack = w[:, :, 0].permute(2, 1, 3, 0).reshape(5, 28, 15)
+        pack = torch.nn.functional.pad(pack, (0, 1)).reshape(35, 64)
+        self.register_buffer('wpack', pack.contiguous())
+        self._bias_buffer(conv)
+
+    def forward(self, x):
+        assert x.shape[1] == self.C
+        assert self.wpack.dtype == torch.float32
+        x, n, d, h, w = self._in(x)
+        out = _empty_cl(x, (n, self.K, d, h, w), self.dt)
+        get_cfx(self.device_index).conv155_out(
+            x.data_ptr(), self.wpack.data_ptr(), _ptr(self.bias),
+            out.data_ptr(), n, d, h, w, self.C, self.K, bf16=self.bf16)
+        return out
 
 
-def _down_eligible(m) -> bool:
-    return (isinstance(m, nn.Conv3d)
-            and m.kernel_size == (1, 2, 2) and m.stride == (1, 2, 2)
-            and m.padding == (0, 0, 0) and m.dilation == (1, 1, 1)
-            and m.groups == 1
-            and m.in_channels <= 64 and m.out_channels <= 64)
+# --------------------------------------------------------------------------
+# the surgery: rules, probe, walker
+# --------------------------------------------------------------------------
+# match(m) says whether the rule takes a module, build(m, device_index)
+# makes its replacement, shape(m) is the probe input (None: installed
+# unprobed). A block rule whose probe fails falls back to swapping the
+# block's conv1 and conv2 for `fallback`, unprobed.
+_Rule = namedtuple('_Rule', 'match build shape fallback',
+                   defaults=(None, None))
+
+
+def _block_shape(block):
+    return (1, block.conv1.in_channels, 4, 18, 22)
+
+
+def _shape155(m):
+    return (1, m.in_channels, 3, 14, 19)
+
+
+def _groups(bf16: bool = False):
+    """The module-surgery groups in the engine's order. Each is walked on
+    its own (the probes draw from the global generator in walk order); for
+    a child the first matching rule of the walked group applies."""
+    def of(cls):
+        return lambda m, device_index: cls(m, device_index, bf16=bf16)
+
+    if bf16:
+        blocks = (_Rule(lambda m: _block_like(m, _eligible_bf16),
+                        CfxResBlockBF16, _block_shape, CfxConv3dBF16),
+                  _Rule(_eligible_bf16, CfxConv3dBF16))
+    else:
+        blocks = (_Rule(_resblock_like, CfxResBlock, _block_shape,
+                        CfxConv3d),
+                  _Rule(_miopen_resblock_like, CfxMiopenResBlock,
+                        _block_shape),
+                  _Rule(_eligible, CfxConv3d))
+    return {
+        'resblock': blocks,
+        'updown': (_Rule(lambda m: _up_eligible(m, bf16), of(CfxUpConv3d),
+                         lambda m: (1, m.in_channels, 3, 12, 16)),),
+        'conv_in': (_Rule(_conv155_eligible, of(CfxConvIn155), _shape155),),
+        'conv_out': (_Rule(_conv155_out_eligible, of(CfxConvOut155),
+                           _shape155),),
+    }
 
 
 @torch.no_grad()
-def _updown_matches(orig, repl, dev, bf16):
-    x = torch.randn(1, repl.C, 3, 12, 16, device=dev)
+def _probe(orig, repl, shape, dev, bf16, tol) -> bool:
+    """Functional probe at surgery time: the replacement must reproduce the
+    original forward on a random input (guards against user modules that
+    merely LOOK like a ResBlock, and against a kernel that is wrong on
+    this machine)."""
+    x = torch.randn(*shape, device=dev)
     if bf16:
         x = x.to(torch.bfloat16)
-    x = x.contiguous(memory_format=torch.channels_last_3d)
+    x = x.contiguous(memory_format=_CL)
     want = orig.to(dev)(x).float()
     got = repl(x).float()
-    tol = 0.05 if bf16 else 1e-4
     return bool(torch.allclose(got, want, rtol=tol, atol=tol))
+
+
+def _walk(model: nn.Module, rules, dev, device_index: int = 0,
+          bf16: bool = False) -> int:
+    """Apply one group of rules in-place; returns the replacement count."""
+    tol = 0.05 if bf16 else 1e-4
+    count = 0
+    detached = set()  # swapped-out originals (their convs must not re-count)
+    for parent in list(model.modules()):  # snapshot: we mutate the tree
+        if id(parent) in detached:
+            continue
+        for name, child in list(parent.named_children()):
+            rule = next((r for r in rules if r.match(child)), None)
+            if rule is None:
+                continue
+            repl = rule.build(child, device_index).to(dev)
+            if rule.shape is None or _probe(child, repl, rule.shape(child),
+                                            dev, bf16, tol):
+                setattr(parent, name, repl)
+                detached.add(id(child))
+                count += 1
+            elif rule.fallback is not None:
+                # forward does something else: swap the lone convs
+                for cn in ('conv1', 'conv2'):
+                    setattr(child, cn,
+                            rule.fallback(getattr(child, cn),
+                                          device_index).to(dev))
+                    count += 1
+    return count
+
+
+def _surgery(model, group, device_index, bf16) -> int:
+    return _walk(model, _groups(bf16)[group], f'cuda:{device_index}',
+                 device_index, bf16)
+
+
+def maybe_accelerate(model: nn.Module, device_index: int = 0) -> int:
+    """Replace eligible ResBlocks (fused) and lone convs in-place;
+    returns the replacement count."""
+    return _surgery(model, 'resblock', device_index, False)
+
+
+def maybe_accelerate_bf16(model: nn.Module, device_index: int = 0) -> int:
+    """bf16 surgery (widths where the bf16 ring is instantiated); same
+    functional-probe guard as the f32 path."""
+    return _surgery(model, 'resblock', device_index, True)
 
 
 def accelerate_updown(model: nn.Module, device_index: int = 0,
                       bf16: bool = False) -> int:
-    """Swap eligible up/down-sampling convs in-place; returns count."""
-    count = 0
-    dev = f'cuda:{device_index}'
-    for parent in list(model.modules()):
-        for name, child in list(parent.named_children()):
-            repl = None
-            if _up_eligible(child, bf16):
-                repl = CfxUpConv3d(child, device_index, bf16=bf16).to(dev)
-            if repl is not None and _updown_matches(child, repl, dev, bf16):
-                setattr(parent, name, repl)
-                count += 1
-    return count
+    """Swap eligible up-sampling convs in-place; returns count."""
+    return _surgery(model, 'updown', device_index, bf16)
+
+
+def accelerate_conv_in(model: nn.Module, device_index: int = 0,
+                       bf16: bool = False) -> int:
+    """Swap the eligible single-channel (1,5,5) input convs; returns
+    count."""
+    return _surgery(model, 'conv_in', device_index, bf16)
+
+
+def accelerate_conv_out(model: nn.Module, device_index: int = 0,
+                        bf16: bool = False) -> int:
+    """Swap the eligible 28 -> 3 (1,5,5) output convs for the MFMA kernel;
+    returns count. It beats MIOpen at both dtypes (13.6x bf16, 5.2x f32,
+    profiles/convout_mfma.json), so callers swap unconditionally."""
+    return _surgery(model, 'conv_out', device_index, bf16)
 
 
 def fuse_up_skip_adds(model: nn.Module, is_up=None):
@@ -570,7 +617,7 @@ def accelerate_up_skip(model: nn.Module, device_index: int = 0,
             return model, 0
         for shape in ((2, 16, 24), (3, 32, 16)):
             x = torch.randn(1, in_channels, *shape, device=dev).contiguous(
-                memory_format=torch.channels_last_3d)
+                memory_format=_CL)
             if not torch.allclose(fused(x), model(x), rtol=1e-4,
                                   atol=1e-4):
                 return model, 0
@@ -579,153 +626,15 @@ def accelerate_up_skip(model: nn.Module, device_index: int = 0,
         return model, 0
 
 
-class CfxConvIn155(nn.Module):
-    """Drop-in for nn.Conv3d(1, K, (1,5,5), padding=(0,2,2)) — the RSUNet
-    input conv. MIOpen's implicit GEMM degenerates on the single input
-    channel (measured 38.8 ms bf16 / 6.8 ms f32 per batch-24 launch vs
-    ~0.5 ms algorithmic); csrc/updown.hip runs it as a 2-D stencil."""
-
-    def __init__(self, conv: nn.Conv3d, device_index: int = 0,
-                 bf16: bool = False):
-        super().__init__()
-        self.K = conv.out_channels
-        self.device_index = device_index
-        self.bf16 = bf16
-        w = conv.weight.detach().float()      # (K, 1, 1, 5, 5)
-        dt = torch.bfloat16 if bf16 else torch.float32
-        self.register_buffer('wpack',
-                             w.reshape(self.K, 25).to(dt).contiguous())
-        if conv.bias is not None:
-            self.register_buffer('bias', conv.bias.detach().float())
-        else:
-            self.bias = None
-
-    def forward(self, x):
-        x = x.contiguous(memory_format=torch.channels_last_3d)
-        n, c, d, h, w = x.shape
-        assert c == 1
-        dt = torch.bfloat16 if self.bf16 else torch.float32
-        assert x.dtype == dt
-        out = torch.empty((n, self.K, d, h, w), dtype=dt, device=x.device,
-                          memory_format=torch.channels_last_3d)
-        get_cfx(self.device_index).conv155_c1(
-            x.data_ptr(), self.wpack.data_ptr(),
-            self.bias.data_ptr() if self.bias is not None else None,
-            out.data_ptr(), n, d, h, w, self.K, bf16=self.bf16)
-        return out
-
-
-def _conv155_eligible(m) -> bool:
-    return (isinstance(m, nn.Conv3d) and m.kernel_size == (1, 5, 5)
-            and m.stride == (1, 1, 1) and m.padding == (0, 2, 2)
-            and m.dilation == (1, 1, 1) and m.groups == 1
-            and m.in_channels == 1 and m.out_channels <= 32)
-
-
-@torch.no_grad()
-def _conv155_matches(orig, repl, dev, bf16):
-    x = torch.randn(1, 1, 3, 14, 19, device=dev)
-    if bf16:
-        x = x.to(torch.bfloat16)
-    x = x.contiguous(memory_format=torch.channels_last_3d)
-    want = orig.to(dev)(x).float()
-    got = repl(x).float()
-    tol = 0.05 if bf16 else 1e-4
-    return bool(torch.allclose(got, want, rtol=tol, atol=tol))
-
-
-def accelerate_conv_in(model: nn.Module, device_index: int = 0,
-                       bf16: bool = False) -> int:
-    """Swap the eligible single-channel (1,5,5) input convs; returns
-    count."""
-    count = 0
-    dev = f'cuda:{device_index}'
-    for parent in list(model.modules()):
-        for name, child in list(parent.named_children()):
-            if _conv155_eligible(child):
-                repl = CfxConvIn155(child, device_index, bf16=bf16).to(dev)
-                if _conv155_matches(child, repl, dev, bf16):
-                    setattr(parent, name, repl)
-                    count += 1
-    return count
-
-
-class CfxConvOut155(nn.Module):
-    """Drop-in for nn.Conv3d(28, 3, (1,5,5), padding=(0,2,2)) — the
-    RSUNet output conv. MIOpen's bf16 implicit GEMM degenerates on the
-    tiny K (measured 38.6 ms per batch-24 launch vs 2.85 ms here;
-    f32 at batch 12 x 20: 6.76 ms vs 1.29 ms, profiles/convout_mfma.json).
-    28 -> 3 only: the five x-taps are folded into the MFMA's output
-    dimension (csrc/updown.hip)."""
-
-    def __init__(self, conv: nn.Conv3d, device_index: int = 0,
-                 bf16: bool = False):
-        super().__init__()
-        self.C = conv.in_channels
-        self.K = conv.out_channels
-        assert (self.C, self.K) == (28, 3), 'conv_out kernel is 28 -> 3'
-        self.device_index = device_index
-        self.bf16 = bf16
-        w = conv.weight.detach().float()      # (K, C, 1, 5, 5)
-        if bf16:                              # the kernel multiplies in f32
-            w = w.to(torch.bfloat16).float()
-        # B fragments of the 35 K-steps: [dy*7 + c//4][(c%4)*16 + j] with
-        # j = dx*3 + k and a zero 16th column
-        pack = w[:, :, 0].permute(2, 1, 3, 0).reshape(5, 28, 15)
-        pack = torch.nn.functional.pad(pack, (0, 1)).reshape(35, 64)
-        self.register_buffer('wpack', pack.contiguous())
-        if conv.bias is not None:
-            self.register_buffer('bias', conv.bias.detach().float())
-        else:
-            self.bias = None
-
-    def forward(self, x):
-        x = x.contiguous(memory_format=torch.channels_last_3d)
-        n, c, d, h, w = x.shape
-        dt = torch.bfloat16 if self.bf16 else torch.float32
-        assert x.dtype == dt and c == self.C
-        assert self.wpack.dtype == torch.float32
-        out = torch.empty((n, self.K, d, h, w), dtype=dt, device=x.device,
-                          memory_format=torch.channels_last_3d)
-        get_cfx(self.device_index).conv155_out(
-            x.data_ptr(), self.wpack.data_ptr(),
-            self.bias.data_ptr() if self.bias is not None else None,
-            out.data_ptr(), n, d, h, w, self.C, self.K, bf16=self.bf16)
-        return out
-
-
-def _conv155_out_eligible(m) -> bool:
-    return (isinstance(m, nn.Conv3d) and m.kernel_size == (1, 5, 5)
-            and m.stride == (1, 1, 1) and m.padding == (0, 2, 2)
-            and m.dilation == (1, 1, 1) and m.groups == 1
-            and m.in_channels == 28 and m.out_channels == 3)
-
-
-def accelerate_conv_out(model: nn.Module, device_index: int = 0,
-                        bf16: bool = False) -> int:
-    """Swap the eligible 28 -> 3 (1,5,5) output convs for the MFMA kernel;
-    returns count. It beats MIOpen at both dtypes
-    (profiles/convout_mfma.json), so callers swap unconditionally."""
-    count = 0
-    dev = f'cuda:{device_index}'
-    for parent in list(model.modules()):
-        for name, child in list(parent.named_children()):
-            if _conv155_out_eligible(child):
-                repl = CfxConvOut155(child, device_index, bf16=bf16).to(dev)
-                if _conv155_matches_generic(child, repl, dev, bf16,
-                                            channels=repl.C):
-                    setattr(parent, name, repl)
-                    count += 1
-    return count
-
-
-@torch.no_grad()
-def _conv155_matches_generic(orig, repl, dev, bf16, channels=1):
-    x = torch.randn(1, channels, 3, 14, 19, device=dev)
-    if bf16:
-        x = x.to(torch.bfloat16)
-    x = x.contiguous(memory_format=torch.channels_last_3d)
-    want = orig.to(dev)(x).float()
-    got = repl(x).float()
-    tol = 0.05 if bf16 else 1e-4
-    return bool(torch.allclose(got, want, rtol=tol, atol=tol))
+def accelerate_all(model: nn.Module, device_index: int = 0,
+                   bf16: bool = False, in_channels: int = 1):
+    """The engine's whole surgery: every group of _groups in order, then
+    (f32 only) the decoder's `up(x) + skip` adds move into the up-conv's
+    epilogue. Returns (model, swapped module count, fused add count); the
+    model comes back as a GraphModule when adds were fused."""
+    count = sum(_surgery(model, group, device_index, bf16)
+                for group in _groups(bf16))
+    upskip = 0
+    if not bf16:
+        model, upskip = accelerate_up_skip(model, device_index, in_channels)
+    return model, count, upskip

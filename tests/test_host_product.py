@@ -337,6 +337,120 @@ def test_fastconv_eligibility_rules():
     assert len(blocks) == 4  # the two 28- and two 36-wide ResBlocks
 
 
+def _fresh_rsunet():
+    import copy
+    from chunkflow_amd.model_loader import load_source
+    src = load_source(os.path.join(
+        os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+        'examples', 'nets', 'rsunet.py'))
+    return copy.deepcopy(src.InstantiatedModel).eval()
+
+
+def _walk_groups(monkeypatch, net, bf16, verdict):
+    """every surgery group in order on the CPU, the probe replaced by a
+    stub that answers `verdict`; returns the per-group counts"""
+    from chunkflow_amd import fastconv as fc
+    probed = []
+
+    def stub(orig, repl, shape, dev, bf16_, tol):
+        probed.append((type(repl).__name__, tuple(shape), bf16_, tol))
+        return verdict
+
+    monkeypatch.setattr(fc, '_probe', stub)
+    counts = [fc._walk(net, rules, 'cpu', 0, bf16)
+              for rules in fc._groups(bf16).values()]
+    return counts, probed
+
+
+def _classes(net):
+    return {name: type(m).__name__ for name, m in net.named_modules()}
+
+
+def test_surgery_walker_f32_probe_true(monkeypatch):
+    """The rule-driven walker on the RSUNet, f32 groups in the engine's
+    order: 7 ResBlocks (a detached block's convs are not visited again,
+    or the count would be higher), 3 up-convs, conv_in, conv_out."""
+    net = _fresh_rsunet()
+    keys = list(net.state_dict())
+    counts, probed = _walk_groups(monkeypatch, net, False, True)
+    assert counts == [7, 3, 1, 1]
+    got = _classes(net)
+    want = {'enc.0': 'CfxResBlock', 'enc.1': 'CfxResBlock',
+            'enc.2': 'CfxMiopenResBlock', 'enc.3': 'CfxMiopenResBlock',
+            'dec.0': 'CfxResBlock', 'dec.1': 'CfxResBlock',
+            'dec.2': 'CfxMiopenResBlock',
+            'up.0': 'CfxUpConv3d', 'up.1': 'CfxUpConv3d',
+            'up.2': 'CfxUpConv3d',
+            'down.0': 'Conv3d', 'down.1': 'Conv3d', 'down.2': 'Conv3d',
+            'conv_in': 'CfxConvIn155', 'conv_out': 'CfxConvOut155'}
+    assert {k: got[k] for k in want} == want
+    assert got['enc.0.c1'] == got['dec.1.c2'] == 'CfxConv3d'
+    assert [net.enc[i].c1.C for i in (0, 1)] == [28, 36]
+    assert [net.enc[i].C for i in (2, 3)] == [48, 64]
+    assert net.dec[2].C == 48
+    # the probes each rule asks for: shape, dtype and tolerance
+    assert probed == (
+        [('CfxResBlock', (1, 28, 4, 18, 22), False, 1e-4),
+         ('CfxResBlock', (1, 36, 4, 18, 22), False, 1e-4),
+         ('CfxMiopenResBlock', (1, 48, 4, 18, 22), False, 1e-4),
+         ('CfxMiopenResBlock', (1, 64, 4, 18, 22), False, 1e-4),
+         ('CfxResBlock', (1, 28, 4, 18, 22), False, 1e-4),
+         ('CfxResBlock', (1, 36, 4, 18, 22), False, 1e-4),
+         ('CfxMiopenResBlock', (1, 48, 4, 18, 22), False, 1e-4)]
+        + [('CfxUpConv3d', (1, c, 3, 12, 16), False, 1e-4)
+           for c in (36, 48, 64)]
+        + [('CfxConvIn155', (1, 1, 3, 14, 19), False, 1e-4),
+           ('CfxConvOut155', (1, 28, 3, 14, 19), False, 1e-4)])
+    # buffer names as before the walker: wtap/bias, w1/b1/w2/b2, wpack
+    new_keys = set(net.state_dict())
+    assert {'enc.0.c1.wtap', 'enc.0.c1.bias', 'enc.2.w1', 'enc.2.b1',
+            'enc.2.w2', 'enc.2.b2', 'up.0.wpack', 'up.0.bias',
+            'conv_in.wpack', 'conv_in.bias', 'conv_out.wpack',
+            'conv_out.bias', 'down.0.weight'} <= new_keys
+    assert len(new_keys) == len(keys)
+
+
+def test_surgery_walker_bf16_probe_true(monkeypatch):
+    from chunkflow_amd import fastconv as fc
+    assert fc.BF16_WIDTHS == (28, 36)  # the default the counts assume
+    net = _fresh_rsunet()
+    counts, probed = _walk_groups(monkeypatch, net, True, True)
+    assert counts == [4, 2, 1, 1]
+    got = _classes(net)
+    want = {'enc.0': 'CfxResBlockBF16', 'enc.1': 'CfxResBlockBF16',
+            'dec.0': 'CfxResBlockBF16', 'dec.1': 'CfxResBlockBF16',
+            'enc.2': 'ResBlock', 'enc.3': 'ResBlock', 'dec.2': 'ResBlock',
+            'enc.0.c1': 'CfxConv3dBF16', 'enc.2.conv1': 'Conv3d',
+            'up.0': 'CfxUpConv3d', 'up.1': 'CfxUpConv3d',
+            'up.2': 'ConvTranspose3d',
+            'conv_in': 'CfxConvIn155', 'conv_out': 'CfxConvOut155'}
+    assert {k: got[k] for k in want} == want
+    assert net.up[0].bf16 and net.conv_in.bf16 and net.conv_out.bf16
+    assert all(p[2] is True and p[3] == 0.05 for p in probed)
+    assert len(probed) == 8
+
+
+def test_surgery_walker_probe_false_falls_back_to_lone_convs(monkeypatch):
+    """A hand-kernel block that fails the probe keeps its own forward and
+    gets its two convs swapped, unprobed; nothing else is installed."""
+    net = _fresh_rsunet()
+    blocks = {n: m for n, m in net.named_modules()
+              if n.startswith(('enc.', 'dec.')) and n.count('.') == 1}
+    counts, probed = _walk_groups(monkeypatch, net, False, False)
+    assert counts == [8, 0, 0, 0]
+    assert len(probed) == 12   # every probed rule asked, none installed
+    got = _classes(net)
+    for name, block in blocks.items():
+        assert net.get_submodule(name) is block   # the original object
+        # levels 0 and 1 are the 28- and 36-wide blocks
+        want = 'CfxConv3d' if name[-1] in '01' else 'Conv3d'
+        assert got[name + '.conv1'] == got[name + '.conv2'] == want, name
+    assert sum(v == 'CfxConv3d' for v in got.values()) == 8
+    for name in ('up.0', 'up.1', 'up.2'):
+        assert got[name] == 'ConvTranspose3d'
+    assert got['conv_in'] == got['conv_out'] == 'Conv3d'
+
+
 @pytest.mark.parametrize('seed', [5, 6, 7, 11])
 def test_normalize_contrast_vs_live_reference(seed):
     """The contrast oracle is BIT-EQUAL to the reference

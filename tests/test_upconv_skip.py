@@ -251,3 +251,45 @@ def test_rewritten_rsunet_matches_surgery_only():
     assert count == n_up == len(fc.UP_SURGERY_WIDTHS_F32)
     assert fused is not net
     torch.testing.assert_close(fused(x), want, rtol=1e-4, atol=1e-4)
+
+
+@gpu
+@torch.no_grad()
+@pytest.mark.parametrize('bf16', [False, True], ids=['f32', 'bf16'])
+def test_accelerate_all_is_the_five_passes_in_order(bf16):
+    """accelerate_all against the public passes called one by one in the
+    engine's order, on two copies of one RSUNet: equal counts, the same
+    class at every module name and bit-equal outputs. 16 x 24 is the
+    smallest input through all four levels; it leaves partial ring tiles
+    at the top level and 2 x 3 at the bottom. Both surgeries start from
+    the same generator state, so their probes see the same inputs."""
+    import copy
+    from chunkflow_amd import fastconv as fc
+    net = _rsunet().cuda()
+    if bf16:
+        net = net.to(torch.bfloat16)
+    net = net.to(memory_format=CL)
+    one, two = copy.deepcopy(net), copy.deepcopy(net)
+
+    torch.manual_seed(11)
+    n = (fc.maybe_accelerate_bf16 if bf16 else fc.maybe_accelerate)(one, 0)
+    n += fc.accelerate_updown(one, 0, bf16=bf16)
+    n += fc.accelerate_conv_in(one, 0, bf16=bf16)
+    n += fc.accelerate_conv_out(one, 0, bf16=bf16)
+    n_add = 0
+    if not bf16:
+        one, n_add = fc.accelerate_up_skip(one, 0, 1)
+
+    torch.manual_seed(11)
+    two, m, m_add = fc.accelerate_all(two, 0, bf16, 1)
+
+    assert (n, n_add) == (m, m_add) == ((8, 0) if bf16 else (12, 3))
+    names = {k: type(v).__name__ for k, v in one.named_modules()}
+    assert names == {k: type(v).__name__ for k, v in two.named_modules()}
+    assert names['enc.0'] == ('CfxResBlockBF16' if bf16 else 'CfxResBlock')
+    torch.manual_seed(12)
+    x = torch.randn(1, 1, 3, 16, 24, device='cuda')
+    if bf16:
+        x = x.to(torch.bfloat16)
+    x = x.contiguous(memory_format=CL)
+    assert torch.equal(one(x), two(x))
