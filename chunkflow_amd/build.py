@@ -11,7 +11,10 @@ SRC_CONV = os.path.join(PKG_DIR, 'csrc', 'conv.hip')
 SRC_UPDOWN = os.path.join(PKG_DIR, 'csrc', 'updown.hip')
 SRC_DOWNSAMPLE = os.path.join(PKG_DIR, 'csrc', 'downsample.hip')
 SRC_LABELS = os.path.join(PKG_DIR, 'csrc', 'labels.hip')
+SRC_WATERSHED = os.path.join(PKG_DIR, 'csrc', 'watershed.hip')
 SRC_INT = os.path.join(PKG_DIR, 'csrc', 'cfx_internal.h')
+SRC_UF = os.path.join(PKG_DIR, 'csrc', 'cc_unionfind.h')
+SRC_TABLE = os.path.join(PKG_DIR, 'csrc', 'label_table.h')
 HEADER = os.path.join(PKG_DIR, '..', 'include', 'chunkflow_amd.h')
 
 
@@ -21,7 +24,8 @@ def so_is_fresh() -> bool:
     so_mtime = os.path.getmtime(SO_PATH)
     return all(os.path.getmtime(p) <= so_mtime
                for p in (SRC, SRC_CC, SRC_IMG, SRC_CONV, SRC_UPDOWN,
-                         SRC_DOWNSAMPLE, SRC_LABELS, SRC_INT, HEADER))
+                         SRC_DOWNSAMPLE, SRC_LABELS, SRC_WATERSHED, SRC_INT,
+                         SRC_UF, SRC_TABLE, HEADER))
 
 
 def build(force: bool = False) -> str:
@@ -35,7 +39,8 @@ def build(force: bool = False) -> str:
     cmd = [
         'hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17',
         '-ffp-contract=off', '-fPIC', '-shared', SRC, SRC_CC, SRC_IMG,
-        SRC_CONV, SRC_UPDOWN, SRC_DOWNSAMPLE, SRC_LABELS, '-o', SO_PATH,
+        SRC_CONV, SRC_UPDOWN, SRC_DOWNSAMPLE, SRC_LABELS, SRC_WATERSHED,
+        '-o', SO_PATH,
     ]
     subprocess.run(cmd, check=True)
     return SO_PATH

@@ -25,6 +25,9 @@
 // shared context/error plumbing lives in cfx.hip; this file is compiled
 // into the same shared object (see csrc/Makefile and build.py)
 #include "cfx_internal.h"
+// cc_ld / cc_st / cc_find_ro / cc_find / cc_union: every access to the
+// parent array goes through them (the reasons are written there)
+#include "cc_unionfind.h"
 
 namespace {
 
@@ -38,63 +41,6 @@ __device__ __constant__ int BWD[13][3] = {
     {-1, -1, 0}, {-1, 1, 0},
     {-1, -1, -1}, {-1, -1, 1}, {-1, 1, -1}, {-1, 1, 1},    // 26 (corners)
 };
-
-// Every parent access is an agent-scope relaxed atomic (lowered to an
-// sc1 load/store that bypasses the per-CU L1): a mid-chain node j can only
-// ever READ as "p[j]==j" from a stale init-era L1 line — plain loads
-// produced exactly that (~0.7% of voxels compressed to a non-root on real
-// volumes; MI355X_MICROARCH.md §inter-workgroup visibility).
-__device__ inline unsigned int cc_ld(const unsigned int* p, unsigned int x) {
-    return __hip_atomic_load(&p[x], __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ inline void cc_st(unsigned int* p, unsigned int x,
-                             unsigned int v) {
-    __hip_atomic_store(&p[x], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// read-only find: used where a halving store could overwrite another
-// thread's already-compressed root (k_cc_compress: thread T2 shortcutting
-// THROUGH node i with a stale-read mid-chain ancestor would clobber T1's
-// final parent[i]=root store — observed as ~1e-4 of voxels labeled from
-// unwritten scratch)
-__device__ inline unsigned int cc_find_ro(const unsigned int* p,
-                                          unsigned int x) {
-    unsigned int px = cc_ld(p, x);
-    while (px != x) {
-        x = px;
-        px = cc_ld(p, x);
-    }
-    return x;
-}
-
-__device__ inline unsigned int cc_find(unsigned int* __restrict__ p,
-                                       unsigned int x) {
-    unsigned int px = cc_ld(p, x);
-    while (px != x) {
-        unsigned int ppx = cc_ld(p, px);
-        cc_st(p, x, ppx);  // path halving (ancestor store, benign race)
-        x = ppx;
-        px = cc_ld(p, x);
-    }
-    return x;
-}
-
-__device__ inline void cc_union(unsigned int* __restrict__ p,
-                                unsigned int a, unsigned int b) {
-    while (true) {
-        a = cc_find(p, a);
-        b = cc_find(p, b);
-        if (a == b) return;
-        unsigned int lo = a < b ? a : b;
-        unsigned int hi = a ^ b ^ lo;
-        unsigned int old = atomicCAS(&p[hi], hi, lo);
-        if (old == hi) return;
-        a = old;
-        b = lo;
-    }
-}
 
 // "same component?" predicates: v is the voxel array, fg() tells foreground
 // from a voxel's value, same() whether a FOREGROUND voxel of value a unites
@@ -232,6 +178,46 @@ __global__ void k_nonzero_u8(const unsigned char* __restrict__ in,
     for (; i < n; i += stride) fg[i] = in[i] != 0 ? 1 : 0;
 }
 
+}  // namespace
+
+// count / host scan / rank: shared with watershed.hip (cc_unionfind.h)
+int cc_rank_roots(cfx_ctx* ctx, const unsigned int* parent, long long n,
+                  unsigned int* newlabel, long long* total_out) {
+    int nchunks = (int)((n + SCAN_CHUNK - 1) / SCAN_CHUNK);
+    if (ctx->cc_counts_cap < nchunks) {
+        if (ctx->cc_counts) (void)hipFree(ctx->cc_counts);
+        ctx->cc_counts = nullptr;
+        ctx->cc_counts_cap = 0;
+        CFX_CHECK(hipMalloc(&ctx->cc_counts,
+                            (size_t)nchunks * sizeof(unsigned int)));
+        ctx->cc_counts_cap = nchunks;
+    }
+    hipLaunchKernelGGL(k_cc_count, dim3(nchunks), dim3(64), 0, ctx->stream,
+                       parent, n, ctx->cc_counts);
+    // exclusive scan of the (small) per-chunk counts on the host
+    std::vector<unsigned int> counts(nchunks);
+    CFX_CHECK(hipMemcpyAsync(counts.data(), ctx->cc_counts,
+                             (size_t)nchunks * sizeof(unsigned int),
+                             hipMemcpyDeviceToHost, ctx->stream));
+    CFX_CHECK(hipStreamSynchronize(ctx->stream));
+    unsigned long long total = 0;
+    for (int i = 0; i < nchunks; ++i) {
+        unsigned int c = counts[i];
+        counts[i] = (unsigned int)total;
+        total += c;
+    }
+    *total_out = (long long)total;
+    CFX_CHECK(hipMemcpyAsync(ctx->cc_counts, counts.data(),
+                             (size_t)nchunks * sizeof(unsigned int),
+                             hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_cc_rank, dim3(nchunks), dim3(64), 0, ctx->stream,
+                       parent, n, ctx->cc_counts, newlabel);
+    CFX_CHECK(hipGetLastError());
+    return 0;
+}
+
+namespace {
+
 inline int grid_for(long long work, int threads) {
     long long want = (work + threads - 1) / threads;
     return (int)(want < 8192 ? want : 8192);
@@ -268,35 +254,10 @@ int run_cc(cfx_ctx* ctx, P pred, int elem_bytes, const int dims[3],
     hipLaunchKernelGGL(k_cc_compress<P>, dim3(grid_for(n, 256)), dim3(256),
                        0, ctx->stream, pred, labels, n);
 
-    int nchunks = (int)((n + SCAN_CHUNK - 1) / SCAN_CHUNK);
-    if (ctx->cc_counts_cap < nchunks) {
-        if (ctx->cc_counts) (void)hipFree(ctx->cc_counts);
-        ctx->cc_counts = nullptr;
-        ctx->cc_counts_cap = 0;
-        CFX_CHECK(hipMalloc(&ctx->cc_counts,
-                            (size_t)nchunks * sizeof(unsigned int)));
-        ctx->cc_counts_cap = nchunks;
+    if (cc_rank_roots(ctx, labels, n, scratch, n_components)) {
+        prof_drop(ctx, e0);
+        return -1;
     }
-    hipLaunchKernelGGL(k_cc_count, dim3(nchunks), dim3(64), 0, ctx->stream,
-                       labels, n, ctx->cc_counts);
-    // exclusive scan of the (small) per-chunk counts on the host
-    std::vector<unsigned int> counts(nchunks);
-    CFX_CHECK(hipMemcpyAsync(counts.data(), ctx->cc_counts,
-                             (size_t)nchunks * sizeof(unsigned int),
-                             hipMemcpyDeviceToHost, ctx->stream));
-    CFX_CHECK(hipStreamSynchronize(ctx->stream));
-    unsigned long long total = 0;
-    for (int i = 0; i < nchunks; ++i) {
-        unsigned int c = counts[i];
-        counts[i] = (unsigned int)total;
-        total += c;
-    }
-    *n_components = (long long)total;
-    CFX_CHECK(hipMemcpyAsync(ctx->cc_counts, counts.data(),
-                             (size_t)nchunks * sizeof(unsigned int),
-                             hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_cc_rank, dim3(nchunks), dim3(64), 0, ctx->stream,
-                       labels, n, ctx->cc_counts, scratch);
     hipLaunchKernelGGL(k_cc_final<P>, dim3(grid_for(n, 256)), dim3(256), 0,
                        ctx->stream, pred, labels, scratch, labels, n);
     CFX_CHECK(hipGetLastError());

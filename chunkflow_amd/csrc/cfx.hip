@@ -91,6 +91,12 @@ int prof_end(cfx_ctx* ctx, hipEvent_t e0, int kid, double bytes) {
     return 0;
 }
 
+// a timed region that fails between prof_begin and prof_end gives its
+// start event back
+void prof_drop(cfx_ctx* ctx, hipEvent_t e0) {
+    if (ctx->profile) (void)hipEventDestroy(e0);
+}
+
 extern "C" int cfx_profile_enable(cfx_ctx* ctx, int enable) {
     ctx->profile = enable != 0;
     return 0;

@@ -44,5 +44,6 @@ extern thread_local std::string g_err;
 
 int prof_begin(cfx_ctx* ctx, hipEvent_t* e0);
 int prof_end(cfx_ctx* ctx, hipEvent_t e0, int kid, double bytes);
+void prof_drop(cfx_ctx* ctx, hipEvent_t e0);
 
 #endif  // CFX_INTERNAL_H

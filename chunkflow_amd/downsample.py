@@ -181,14 +181,9 @@ def _method(chunk: Chunk) -> str:
         f'only support image or segmentation, but got: {chunk.dtype}')
 
 
-_OPS = {}
-
-
 def _hip_ops(device_index: int):
-    from .ops import HipOps
-    if device_index not in _OPS:
-        _OPS[device_index] = HipOps(device_index)
-    return _OPS[device_index]
+    from .ops import shared_hip_ops
+    return shared_hip_ops(device_index)
 
 
 def downsample(chunk: Chunk, factor=(2, 2, 2)) -> Chunk:

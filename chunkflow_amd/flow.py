@@ -22,6 +22,12 @@ operators (reference chunkflow/flow/flow.py):
 plus the at-least-once resume family (skip-task-by-file, mark-complete,
 skip-all-zero, skip-none — SURVEY.md §5), copy-var/delete-var, and npy
 load/save at the pipeline edge.
+
+One operator has no counterpart in the reference's CLI, which reaches it only
+through its `agglomerate` plugin over the waterz wheel:
+  watershed             fragments of an affinity map (watershed.py; gfx950
+                        union-find on device chunks); plugins/agglomerate.py
+                        completes it to a segmentation
 """
 import json
 import os
@@ -365,6 +371,33 @@ def connected_components(tasks, name, input_chunk_name, output_chunk_name,
             task[output_chunk_name] = connected_component(
                 task[input_chunk_name], threshold=threshold,
                 connectivity=connectivity)
+            task['log']['timer'][name] = time() - start
+        yield task
+
+
+@main.command('watershed')
+@click.option('--name', type=str, default='watershed',
+              help='name of this operator')
+@click.option('--input-chunk-name', '-i', type=str,
+              default=DEFAULT_CHUNK_NAME, help='input chunk name')
+@click.option('--output-chunk-name', '-o', type=str,
+              default=DEFAULT_CHUNK_NAME, help='output chunk name')
+@click.option('--low', type=click.FLOAT, default=0.001,
+              help='edges with an affinity below this are cut.')
+@click.option('--high', type=click.FLOAT, default=0.9999,
+              help='edges with an affinity of at least this always join. '
+                   'With --low T --high T the fragments are the connected '
+                   'components of the affinity graph at T.')
+@operator
+def watershed(tasks, name, input_chunk_name, output_chunk_name, low, high):
+    """Watershed fragments of an affinity map (device chunks stay on the
+    device)."""
+    from .watershed import affinity_fragments
+    for task in tasks:
+        if task is not None:
+            start = time()
+            task[output_chunk_name] = affinity_fragments(
+                task[input_chunk_name], low, high)
             task['log']['timer'][name] = time() - start
         yield task
 

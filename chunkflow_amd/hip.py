@@ -51,6 +51,9 @@ SIGNATURES = {
     'cfx_label_count': (I, [P, P, I, P, P, P, L]),
     'cfx_label_pair_count': (I, [P, P, I, P, P, L, P, I, P, P, L, P, P, L]),
     'cfx_label_mask': (I, [P, P, P, I, P, P, P, L, I, L]),
+    'cfx_affinity_fragments': (I, [P, P, P, F, F, P, P, P]),
+    'cfx_region_graph_runs': (I, [P, P, P, P]),
+    'cfx_region_graph': (I, [P, P, P, P, P, P, P, L]),
     'cfx_hist_u8': (I, [P, P, L, I, P]),
     'cfx_lut_apply_u8': (I, [P, P, L, I, P]),
     'cfx_downsample_avg_u8': (I, [P, P, P, I, P, P]),
@@ -292,6 +295,25 @@ class CfxContext:
                    vals_ptr, capacity, mode, threshold=0):
         self._call('cfx_label_mask', in_ptr, out_ptr, elem_bytes, _i3(dims),
                    keys_ptr, vals_ptr, capacity, mode, threshold)
+
+    # --- affinity maps to segments -------------------------------------------
+    def affinity_fragments(self, aff_ptr, dims, low, high, labels_ptr,
+                           scratch_ptr) -> int:
+        ncomp = ctypes.c_longlong(0)
+        self._call('cfx_affinity_fragments', aff_ptr, _i3(dims), low, high,
+                   labels_ptr, scratch_ptr, ctypes.byref(ncomp))
+        return ncomp.value
+
+    def region_graph_runs(self, frag_ptr, dims) -> int:
+        runs = ctypes.c_longlong(0)
+        self._call('cfx_region_graph_runs', frag_ptr, _i3(dims),
+                   ctypes.byref(runs))
+        return runs.value
+
+    def region_graph(self, frag_ptr, aff_ptr, dims, keys_ptr, counts_ptr,
+                     sums_ptr, capacity):
+        self._call('cfx_region_graph', frag_ptr, aff_ptr, _i3(dims),
+                   keys_ptr, counts_ptr, sums_ptr, capacity)
 
     # --- convolutions --------------------------------------------------------
     def conv3_ndhwc(self, in_ptr, wgt_ptr, bias_ptr, residual_ptr, out_ptr,

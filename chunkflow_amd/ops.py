@@ -333,6 +333,87 @@ class HipOps:
                             capacity, 1, 0)
         return out
 
+    # --- affinity maps to segments (csrc/watershed.hip) ----------------------
+    @staticmethod
+    def _check_affinity(t: torch.Tensor, who: str) -> torch.Tensor:
+        """The map as a contiguous f32 tensor: f16 / bf16 widen exactly."""
+        if t.ndim != 4 or t.shape[0] != 3:
+            raise ValueError(f'{who}: affinity map must be (3, Z, Y, X), '
+                             f'but got shape {tuple(t.shape)}')
+        if t.numel() == 0:
+            raise ValueError(f'{who}: empty affinity map')
+        return t.to(torch.float32).contiguous()
+
+    def affinity_fragments(self, aff: torch.Tensor, low: float,
+                           high: float):
+        """(labels, n): watershed fragments of a (3, Z, Y, X) map as an
+        int32 tensor carrying uint32 labels 1..n, 0 background."""
+        aff = self._check_affinity(aff, 'affinity_fragments')
+        dims = tuple(aff.shape[1:])
+        labels = torch.empty(dims, dtype=torch.int32, device=aff.device)
+        scratch = torch.empty(dims, dtype=torch.int32, device=aff.device)
+        n = self.cfx.affinity_fragments(aff.data_ptr(), dims, float(low),
+                                        float(high), labels.data_ptr(),
+                                        scratch.data_ptr())
+        return labels, n
+
+    def region_graph_table(self, frag: torch.Tensor, aff: torch.Tensor,
+                           capacity: int = None):
+        """(keys, counts, sums, info): the region graph of an int32 fragment
+        volume as a table, key (a << 32) | b for a < b. The table is sized
+        from the number of table operations the kernel will make (a first
+        pass over the fragments alone): every distinct key is sent at least
+        once, so the rows cannot outnumber the operations. `capacity`
+        overrides the sizing (a power of two; too small raises "label
+        table full")."""
+        aff = self._check_affinity(aff, 'region_graph')
+        if frag.dtype != torch.int32:
+            raise TypeError(f'region_graph: device fragments must be int32 '
+                            f'(carrying uint32), but got: {frag.dtype}')
+        if tuple(frag.shape) != tuple(aff.shape[1:]):
+            raise ValueError(f'region_graph: fragments {tuple(frag.shape)} '
+                             f'and affinity map {tuple(aff.shape)} differ '
+                             f'in shape')
+        frag = frag.contiguous()
+        dims = tuple(frag.shape)
+        bound = None
+        if capacity is None:
+            bound = self.cfx.region_graph_runs(frag.data_ptr(), dims)
+            capacity = self.LABEL_TABLE_MIN
+            while capacity < 2 * bound:
+                capacity *= 2
+        keys = torch.empty(capacity, dtype=torch.int64, device=frag.device)
+        counts = torch.empty(capacity, dtype=torch.int32, device=frag.device)
+        sums = torch.empty(capacity, dtype=torch.int64, device=frag.device)
+        self.cfx.region_graph(frag.data_ptr(), aff.data_ptr(), dims,
+                              keys.data_ptr(), counts.data_ptr(),
+                              sums.data_ptr(), capacity)
+        return keys, counts, sums, {'bound': bound, 'capacity': capacity}
+
+    def region_graph(self, frag: torch.Tensor, aff: torch.Tensor):
+        """(a, b, count, sum) int64 tensors, one row per pair of touching
+        fragments a < b, sorted by (a, b)."""
+        keys, counts, sums, _ = self.region_graph_table(frag, aff)
+        used = keys != -1
+        keys, counts, sums = keys[used], counts[used], sums[used]
+        # a < 2^32-1, so a key's sign bit is a's top bit: flipping it turns
+        # signed order into unsigned order
+        order = torch.argsort(torch.bitwise_xor(keys, -2 ** 63))
+        keys = keys[order]
+        return ((keys >> 32) & 0xFFFFFFFF, keys & 0xFFFFFFFF,
+                counts[order].to(torch.int64) & 0xFFFFFFFF, sums[order])
+
+
+_SHARED = {}
+
+
+def shared_hip_ops(device_index: int = 0) -> HipOps:
+    """The one HipOps (context, scratch, profile counters) per device that
+    the operator modules share (segmentation, downsample, watershed)."""
+    if device_index not in _SHARED:
+        _SHARED[device_index] = HipOps(device_index)
+    return _SHARED[device_index]
+
 
 class TorchOps:
     is_hip = False

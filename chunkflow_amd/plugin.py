@@ -41,27 +41,34 @@ def array_to_chunk(arr: Union[np.ndarray, Chunk], voxel_offset: Cartesian,
     return arr
 
 
+def load_plugin(plugin_file_name: str):
+    """The `execute` function of a plugin given by file name, with or
+    without '.py': searched in ./, the package's plugins directory and
+    $CHUNKFLOW_PLUGIN_DIR, in that order."""
+    if not plugin_file_name.endswith('.py'):
+        plugin_file_name += '.py'
+    pkg_plugin_dir = path.join(
+        path.dirname(path.realpath(__file__)), 'plugins')
+    plugin_dirs = ['./', pkg_plugin_dir]
+    if 'CHUNKFLOW_PLUGIN_DIR' in os.environ:
+        plugin_dirs.append(os.environ['CHUNKFLOW_PLUGIN_DIR'])
+    fname = plugin_file_name
+    for d in plugin_dirs:
+        cand = path.join(d, plugin_file_name)
+        if path.exists(cand):
+            fname = cand
+            break
+    assert path.exists(fname), f'did not find plugin: {plugin_file_name}'
+    program = load_source(fname)
+    assert hasattr(program, 'execute'), \
+        f'plugin {fname} must define execute(*inputs, **kwargs)'
+    return program.execute
+
+
 class Plugin:
     def __init__(self, plugin_file_name: str, name: str = 'plugin-1'):
         self.name = name
-        if not plugin_file_name.endswith('.py'):
-            plugin_file_name += '.py'
-        pkg_plugin_dir = path.join(
-            path.dirname(path.realpath(__file__)), 'plugins')
-        plugin_dirs = ['./', pkg_plugin_dir]
-        if 'CHUNKFLOW_PLUGIN_DIR' in os.environ:
-            plugin_dirs.append(os.environ['CHUNKFLOW_PLUGIN_DIR'])
-        fname = plugin_file_name
-        for d in plugin_dirs:
-            cand = path.join(d, plugin_file_name)
-            if path.exists(cand):
-                fname = cand
-                break
-        assert path.exists(fname), f'did not find plugin: {plugin_file_name}'
-        program = load_source(fname)
-        assert hasattr(program, 'execute'), \
-            f'plugin {fname} must define execute(*inputs, **kwargs)'
-        self.execute = program.execute
+        self.execute = load_plugin(plugin_file_name)
 
     def __call__(self, inputs: list, args: str = None):
         voxel_offset = voxel_size = shape = None

@@ -81,14 +81,9 @@ def _check(chunk: Chunk, who: str):
                         f'{chunk.dtype}')
 
 
-_OPS = {}
-
-
 def _hip_ops(device_index: int):
-    from .ops import HipOps
-    if device_index not in _OPS:
-        _OPS[device_index] = HipOps(device_index)
-    return _OPS[device_index]
+    from .ops import shared_hip_ops
+    return shared_hip_ops(device_index)
 
 
 def _ops_for(chunk: Chunk):

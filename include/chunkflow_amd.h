@@ -204,6 +204,42 @@ int cfx_label_mask(cfx_ctx* ctx, const void* in, void* out, int elem_bytes,
                    const unsigned int* vals, long long capacity, int mode,
                    long long threshold);
 
+/* ---- affinity maps to segments (watershed + region graph) -------------- */
+/* aff is f32 (3, D, H, W), contiguous, channels x, y, z: aff[c][v] is the
+ * weight of the edge between voxel v and its predecessor along that axis
+ * (the leading face of each axis belongs to no edge and is never read).
+ * All compares are f32; NaN fails every test. */
+/* Watershed fragments, a steepest-ascent forest: an edge is live iff
+ * w >= low and strong iff live and w >= high; a voxel with a live incident
+ * edge picks the first one in the order -x +x -y +y -z +z whose weight is
+ * the maximum over its live incident edges; fragments are the connected
+ * components under the strong and the picked edges, numbered 1..N by first
+ * voxel in raster order; a voxel without a live incident edge is 0. With
+ * low == high == T these are the components of the edges >= T. labels and
+ * scratch are u32 buffers of D*H*W elements (fewer than 2^32-1), as for
+ * cfx_connected_components. Synchronous. */
+int cfx_affinity_fragments(cfx_ctx* ctx, const float* aff, const int dims[3],
+                           float low, float high, unsigned int* labels,
+                           unsigned int* scratch, long long* n_components);
+/* The region graph of a u32 fragment volume: one row per pair a < b of
+ * different non-zero ids joined by at least one edge, keyed (a << 32) | b in
+ * a table of the kind above with a second value array: counts[slot] is the
+ * number of such edges, sums[slot] the sum of q(w) over them, q(w) =
+ * floor(c * 2^24) with c = w > 0 ? min(w, 1) : 0 (NaN and negative weights
+ * give 0), so a row's mean affinity is sums / (counts * 2^24) and the rows
+ * are bit-exact whatever the order of the adds. The call clears the table
+ * first. capacity is a power of two and at least the number of rows: size
+ * it from cfx_region_graph_runs, which returns the number of table
+ * operations the call makes (one per run of equal pairs within a lane's
+ * stretch of a row), an upper bound on the rows. At most (2^32-1)/3
+ * voxels. Errors: "label table full". Both synchronous. */
+int cfx_region_graph_runs(cfx_ctx* ctx, const unsigned int* frag,
+                          const int dims[3], long long* n_runs);
+int cfx_region_graph(cfx_ctx* ctx, const unsigned int* frag,
+                     const float* aff, const int dims[3],
+                     unsigned long long* keys, unsigned int* counts,
+                     unsigned long long* sums, long long capacity);
+
 /* ---- image normalization (normalize-contrast operator) ----------------- */
 /* zero + accumulate nsec 256-bin u32 histograms, one per contiguous
  * n_per_sec-voxel section of a u8 volume */

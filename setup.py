@@ -18,6 +18,8 @@ setup(
     version='0.1.0',
     description="MI355X-native chunkflow inference hot path",
     packages=find_packages(include=['chunkflow_amd*']),
+    # plugin files are loaded by path (plugin.load_plugin), not imported
+    package_data={'chunkflow_amd': ['plugins/*.py']},
     python_requires='>=3.8',
     entry_points={
         'console_scripts': ['chunkflow = chunkflow_amd.flow:main'],
