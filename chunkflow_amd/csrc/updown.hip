@@ -5,13 +5,15 @@
 // HBM-streaming work (a C-vector read + K-vector write per spatial
 // position; no tap overlap), and MIOpen's bf16 bwd_data implicit GEMM is
 // far off that roofline on the big up-conv (measured 8.0 ms vs ~0.2 ms
-// algorithmic at 36->28 x 128^2, profiles/updown_probe_r02.json). These
-// kernels are VALU streams: input row and weights staged to LDS in
+// algorithmic at 36->28 x 128^2, profiles/updown_probe_r02.json). The
+// k_upconv2 / k_downconv2 kernels are VALU streams: input row and weights
+// staged to LDS in
 // batched coalesced loads (a per-load global read next to its use costs a
 // full vmcnt drain — the round-1 staging lesson), per-thread accumulators
 // over 8 x-positions so each weight vector is read once per c. The f32
 // up-conv of MFMA-shaped widths and the 28 -> 3 output conv run on the f32
-// matrix cores instead (k_upconv2_mfma, k_conv155_out_mfma below).
+// matrix cores instead (k_upconv2_mfma, k_conv155_out_mfma below), and so
+// does the 1 -> 28 input conv (k_conv155_in_mfma).
 //
 // Layouts: NDHWC (channels_last_3d); weights packed
 // [parity q=(py<<1)|px][C][K] (stored in LDS as [c][k][q] float4 so one
@@ -67,6 +69,10 @@ __device__ __forceinline__ void stf<float>(float* p, float v) { *p = v; }
 template <>
 __device__ __forceinline__ void stf<cfx_bf16>(cfx_bf16* p, float v) {
     *p = __float2bfloat16(v);
+}
+
+__device__ __forceinline__ unsigned short bf16_bits(float v) {
+    return ((__hip_bfloat16_raw)__float2bfloat16(v)).x;
 }
 
 // cooperative stage of `rows` input rows (each `xn` positions x C
@@ -409,130 +415,185 @@ __global__ __launch_bounds__(256, 2) void k_downconv2(
     }
 }
 
-// ---- input conv (1,5,5), pad (0,2,2), single input channel ---------------
+// ---- input conv (1,5,5), pad (0,2,2), single input channel, on the MFMA --
 // RSUNet's conv_in (1 -> 28). MIOpen's implicit GEMM collapses to a
 // degenerate K-dim=25 GEMM here and runs ~39 ms (bf16) / ~7 ms (f32) per
-// batch-24 launch vs ~0.5 ms of algorithmic traffic. Plain 2-D stencil:
-// 5 input rows staged to LDS, per-thread weights in registers, PX
-// contiguous x positions per thread so each input value loads once.
-// out[n,z,y,x,k] = bias[k] + sum_{dy,dx} in[n,z,y+dy-2,x+dx-2] * w[k][tap]
-template <typename T, int XI, int KC>  // KC: compile-time K (0 = runtime)
-__global__ __launch_bounds__(256, 2) void k_conv155_c1(
-    const T* __restrict__ in, const T* __restrict__ wgt,
-    const float* __restrict__ bias, T* __restrict__ out, int N, int D,
-    int H, int W, int K_rt) {
-    const int K = KC > 0 ? KC : K_rt;
-    // thread = one output position, computing ALL K: the K outputs of one
-    // position are contiguous in NDHWC, so each thread's stores are a
-    // K-element run and a wave's stores coalesce (the k-parallel variant
-    // wrote 2-byte strided singles and was store-issue-bound, 5.3 ms)
-    __shared__ float s_in[5][XI + 4];
-    __shared__ float s_w[32 * 28];        // rows padded 25 -> 28 (16 B)
-    const int tid = threadIdx.x;          // position slot (XI == 256)
-    const int nz = blockIdx.z;
-    const int y = blockIdx.y;
-    const int x0 = blockIdx.x * XI;
+// batch-24 launch. The VALU stencil this replaces (one thread per position,
+// 25*K separate multiplies and adds under -ffp-contract=off, 7*K broadcast
+// weight reads) took 1.02 ms for the 440 MB it writes at 12x20x256x256.
+// out[n,z,y,x,k] = bias[k] + sum_t in[n,z,y+t/5-2,x+t%5-2] * w[k][t]
+//
+// As a GEMM: M = 16 consecutive x of one row (one tile), K = the 25 taps
+// padded to 28 = 7 steps of v_mfma_f32_16x16x4_f32, N = K outputs padded
+// to 32 = 2 column tiles; 14 MFMAs per tile. The accumulators start from
+// the bias, so an output is the f32 fma chain over the taps in order.
+//
+// One workgroup = CI_R output rows x CI_S positions of one (n, z) plane:
+// it stages (CI_R+4) x (CI_S+4) input values as f32 (zero outside the
+// image in y and x -- a halo row is never a row of the neighbouring
+// plane), 3.2 KB, loaded as one batch from clamped addresses and zeroed by
+// a select after the load. Wave w then owns the 16-position column w of
+// the strip and walks the rows with no further workgroup barrier.
+// A: lane (i, kk) of step s reads the window value of tap t = 4s+kk for
+// position i -- consecutive i are consecutive LDS words, one conflict-free
+// ds_read_b32 per step; the padding taps t = 25..27 are selected to 0 (not
+// multiplied by a zero weight: inf * 0 would poison the tile).
+// B: 14 dwords per lane, gathered once per workgroup from wgt [K][25],
+// zero for t >= 25 and for columns >= K.
+// Epilogue: a tile's output is ONE contiguous run of 16*K elements, so the
+// accumulators are bounced through a wave-private LDS copy of that run
+// (D[row = position][col = k] -> s_b[position * K + k]; columns >= K are
+// not written) and leave as 4-element pieces, piece f of the run at
+// element 4f: 16-byte stores in f32, 8-byte in bf16. K % 4 != 0 or a
+// misaligned `out` takes scalar stores; partial tiles select at the store.
+// 11.2 KB of LDS, 62 VGPRs + 20 AGPRs: 5 workgroups, i.e. 5 waves per
+// SIMD, per CU (6 in bf16), so one wave's bounce and stores hide under the
+// MFMAs of the others. 12x20x256x256 f32: 0.405 ms for 1.82 GB of in +
+// out, 4.5 TB/s (profiles/conv_in_mfma.json).
+constexpr int CI_R = 8;             // output rows per workgroup
+constexpr int CI_S = 64;            // output positions per workgroup
+constexpr int CI_NW = CI_S / 16;    // waves, one 16-position column each
+constexpr int CI_LW = CI_S + 4;     // staged row, floats
 
-    const long long plane = (long long)nz * H;
-    for (int idx = tid; idx < 5 * (XI + 4); idx += XI) {
-        const int dy = idx / (XI + 4);
-        const int xl = idx % (XI + 4);
-        const int gy = y + dy - 2;
+template <typename T>
+__global__ __launch_bounds__(CI_NW * 64) void k_conv155_in_mfma(
+    const T* __restrict__ in, const T* __restrict__ wgt,
+    const float* __restrict__ bias, T* __restrict__ out, int H, int W,
+    int K, int nstrips, int nrows, int vec_ok) {
+    constexpr int NS = (CI_R + 4) * CI_LW;               // staged values
+    constexpr int PER = (NS + CI_NW * 64 - 1) / (CI_NW * 64);
+    __shared__ float s_in[NS];
+    __shared__ __attribute__((aligned(16))) float s_bounce[CI_NW][16 * 32];
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int ai = lane & 15;   // A row (position) / B, D column
+    const int akk = lane >> 4;  // A, B k / D row group
+    // blockIdx.x = ((n*D + z) * nrows + row group) * nstrips + strip
+    const int strip = (int)blockIdx.x % nstrips;
+    const int rest = (int)blockIdx.x / nstrips;
+    const int y0 = (rest % nrows) * CI_R;
+    const int x0 = strip * CI_S;
+    const long long plane = (long long)(rest / nrows) * H;
+
+    // stage: every load first, from clamped addresses; zeros by select
+    float v[PER];
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+        const int idx = u * (CI_NW * 64) + tid;
+        const int r = idx / CI_LW;
+        const int xl = idx - r * CI_LW;
+        const int cy = min(max(y0 + r - 2, 0), H - 1);
+        const int cx = min(max(x0 + xl - 2, 0), W - 1);
+        v[u] = ldf(&in[(plane + cy) * W + cx]);
+    }
+    // B[k = akk][j = ai] of (step s, column tile t)
+    float b[7][2];
+#pragma unroll
+    for (int s = 0; s < 7; ++s)
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+            b[s][t] = ldf(&wgt[min(16 * t + ai, K - 1) * 25 +
+                               min(4 * s + akk, 24)]);
+    float bj[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+        bj[t] = bias ? bias[min(16 * t + ai, K - 1)] : 0.f;
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+        const int idx = u * (CI_NW * 64) + tid;
+        const int r = idx / CI_LW;
+        const int xl = idx - r * CI_LW;
+        const int gy = y0 + r - 2;
         const int gx = x0 + xl - 2;
         const bool ok = gy >= 0 && gy < H && gx >= 0 && gx < W;
-        s_in[dy][xl] = ok ? ldf(&in[(plane + gy) * W + gx]) : 0.f;
+        if (idx < NS) s_in[idx] = ok ? v[u] : 0.f;
     }
-    for (int idx = tid; idx < K * 28; idx += XI) {
-        const int t = idx % 28;
-        const int k = idx / 28;
-        s_w[idx] = t < 25 ? ldf(&wgt[k * 25 + t]) : 0.f;
-    }
+#pragma unroll
+    for (int s = 0; s < 7; ++s)
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+            b[s][t] = 4 * s + akk < 25 && 16 * t + ai < K ? b[s][t] : 0.f;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) bj[t] = 16 * t + ai < K ? bj[t] : 0.f;
     __syncthreads();
 
-    const int gx = x0 + tid;
-    if (gx >= W) return;
-    // the 5x5 window of this position, registers
-    float v[25];
+    const int xt = x0 + 16 * wave;  // this wave's tile column
+    if (xt >= W) return;
+    const int nvalid = min(16, W - xt);
+    const int rows = min(CI_R, H - y0);
+    float* s_b = s_bounce[wave];
+    // window offset of tap 4s + akk for position ai, row 0 of the strip
+    int aoff[7];
 #pragma unroll
-    for (int dy = 0; dy < 5; ++dy)
+    for (int s = 0; s < 7; ++s) {
+        const int t = min(4 * s + akk, 24);
+        aoff[s] = (t / 5) * CI_LW + (t % 5) + 16 * wave + ai;
+    }
+    const bool apad = 24 + akk >= 25;  // step 6 holds taps 24..27
+    auto a_reads = [&](int ry, float (&a)[7]) {
 #pragma unroll
-        for (int dx = 0; dx < 5; ++dx)
-            v[dy * 5 + dx] = s_in[dy][tid + dx];
-    T* op = out + (plane + y) * (long long)W * K + (long long)gx * K;
-    if (KC > 0 && KC % 4 == 0) {
-        // compile-time K in groups of 4: scalar accumulators packed into
-        // 8-byte vector stores. No register array address-taking (spills
-        // to scratch) and no full k unroll (28x7 hoisted float4 weight
-        // reads blow the register file) — both measured ~10x slower.
-        typedef unsigned int uint2v __attribute__((ext_vector_type(2)));
-        typedef float float2v __attribute__((ext_vector_type(2)));
-#pragma unroll 1
-        for (int k = 0; k < KC; k += 4) {
-            float a0 = bias ? bias[k] : 0.f;
-            float a1 = bias ? bias[k + 1] : 0.f;
-            float a2 = bias ? bias[k + 2] : 0.f;
-            float a3 = bias ? bias[k + 3] : 0.f;
+        for (int s = 0; s < 7; ++s) a[s] = s_in[ry * CI_LW + aoff[s]];
+        a[6] = apad ? 0.f : a[6];
+    };
+
+    float a[7];
+    a_reads(0, a);
+    for (int ry = 0; ry < rows; ++ry) {
+        um_f32x4 acc[2];
 #pragma unroll
-            for (int t4 = 0; t4 < 24; t4 += 4) {
-                const float4 w0 = *reinterpret_cast<const float4*>(
-                    &s_w[k * 28 + t4]);
-                const float4 w1 = *reinterpret_cast<const float4*>(
-                    &s_w[(k + 1) * 28 + t4]);
-                const float4 w2 = *reinterpret_cast<const float4*>(
-                    &s_w[(k + 2) * 28 + t4]);
-                const float4 w3 = *reinterpret_cast<const float4*>(
-                    &s_w[(k + 3) * 28 + t4]);
-                a0 += v[t4] * w0.x + v[t4 + 1] * w0.y + v[t4 + 2] * w0.z +
-                      v[t4 + 3] * w0.w;
-                a1 += v[t4] * w1.x + v[t4 + 1] * w1.y + v[t4 + 2] * w1.z +
-                      v[t4 + 3] * w1.w;
-                a2 += v[t4] * w2.x + v[t4 + 1] * w2.y + v[t4 + 2] * w2.z +
-                      v[t4 + 3] * w2.w;
-                a3 += v[t4] * w3.x + v[t4 + 1] * w3.y + v[t4 + 2] * w3.z +
-                      v[t4 + 3] * w3.w;
+        for (int t = 0; t < 2; ++t)
+            acc[t] = um_f32x4{bj[t], bj[t], bj[t], bj[t]};
+#pragma unroll
+        for (int s = 0; s < 7; ++s)
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+                acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                    a[s], b[s][t], acc[t], 0, 0, 0);
+        // the next row's window, read while the MFMAs drain
+        a_reads(min(ry + 1, rows - 1), a);
+        // D[row = akk*4 + r][col = ai] -> the tile's output run
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+            if (16 * t + ai < K) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    s_b[(akk * 4 + r) * K + 16 * t + ai] = acc[t][r];
             }
-            a0 += v[24] * s_w[k * 28 + 24];
-            a1 += v[24] * s_w[(k + 1) * 28 + 24];
-            a2 += v[24] * s_w[(k + 2) * 28 + 24];
-            a3 += v[24] * s_w[(k + 3) * 28 + 24];
-            if (sizeof(T) == 2) {
-                uint2v u;
-                u.x = (unsigned)((__hip_bfloat16_raw)__float2bfloat16(
-                          a0)).x |
-                      ((unsigned)((__hip_bfloat16_raw)__float2bfloat16(
-                           a1)).x << 16);
-                u.y = (unsigned)((__hip_bfloat16_raw)__float2bfloat16(
-                          a2)).x |
-                      ((unsigned)((__hip_bfloat16_raw)__float2bfloat16(
-                           a3)).x << 16);
-                *reinterpret_cast<uint2v*>(reinterpret_cast<char*>(op) +
-                                           (size_t)k * 2) = u;
-            } else {
-                float2v f01, f23;
-                f01.x = a0;
-                f01.y = a1;
-                f23.x = a2;
-                f23.y = a3;
-                float2v* d =
-                    reinterpret_cast<float2v*>(reinterpret_cast<char*>(op) +
-                                               (size_t)k * 4);
-                d[0] = f01;
-                d[1] = f23;
+        __builtin_amdgcn_wave_barrier();
+
+        T* op = out + ((plane + y0 + ry) * W + xt) * (long long)K;
+        if (vec_ok) {
+            // every piece in registers first, then the stores back to back
+            const int npiece = nvalid * (K >> 2);
+            um_f32x4 p[2];
+#pragma unroll
+            for (int it = 0; it < 2; ++it)
+                p[it] = *reinterpret_cast<const um_f32x4*>(
+                    &s_b[4 * (it * 64 + lane)]);
+#pragma unroll
+            for (int it = 0; it < 2; ++it) {
+                const int f = it * 64 + lane;
+                if (f >= npiece) continue;
+                if (sizeof(T) == 2) {
+                    typedef unsigned ci_u32x2
+                        __attribute__((ext_vector_type(2)));
+                    ci_u32x2 h;
+                    h.x = bf16_bits(p[it][0]) |
+                          ((unsigned)bf16_bits(p[it][1]) << 16);
+                    h.y = bf16_bits(p[it][2]) |
+                          ((unsigned)bf16_bits(p[it][3]) << 16);
+                    reinterpret_cast<ci_u32x2*>(op)[f] = h;
+                } else {
+                    reinterpret_cast<um_f32x4*>(op)[f] = p[it];
+                }
             }
+        } else {
+            const int ne = nvalid * K;
+            for (int e = lane; e < ne; e += 64) stf(&op[e], s_b[e]);
         }
-    } else {
-        for (int k = 0; k < K; ++k) {
-            float acc = bias ? bias[k] : 0.f;
-#pragma unroll
-            for (int t4 = 0; t4 < 24; t4 += 4) {
-                const float4 w4 =
-                    *reinterpret_cast<const float4*>(&s_w[k * 28 + t4]);
-                acc += v[t4] * w4.x + v[t4 + 1] * w4.y +
-                       v[t4 + 2] * w4.z + v[t4 + 3] * w4.w;
-            }
-            acc += v[24] * s_w[k * 28 + 24];
-            stf(&op[k], acc);
-        }
+        __builtin_amdgcn_wave_barrier();  // the run is rewritten next row
     }
 }
 
@@ -545,7 +606,8 @@ __global__ __launch_bounds__(256, 2) void k_conv155_c1(
 // steps of v_mfma_f32_16x16x4_f32), and the output is the shifted sum
 //   out[y][x][k] = bias[k] + sum_dx P[x+dx-2][dx*3+k].
 //
-// Tiling (chosen: fixed tiles, no persistent y-walk). One workgroup =
+// Fixed tiles; since k_conv155_out_ywalk below took the f32 route, this is
+// the bf16 kernel (the f32 figures are kept as the record). One workgroup =
 // CO_R = 6 output rows x CO_S = 60 output positions: it stages 10 input
 // rows x 64 positions (x' = x0-2 .. x0+61, so both 2-column halos come
 // from the workgroup's own strip) in the raw dtype, [row][x][c] with c
@@ -573,10 +635,6 @@ constexpr int CO_S = 60;   // output positions per workgroup (64 staged)
 constexpr int CO_PS = 72;  // P bounce: dwords between j rows
 
 typedef float co_f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned short bf16_bits(float v) {
-    return ((__hip_bfloat16_raw)__float2bfloat16(v)).x;
-}
 
 template <typename T>
 __global__ __launch_bounds__(256, 2) void k_conv155_out_mfma(
@@ -729,6 +787,187 @@ __global__ __launch_bounds__(256, 2) void k_conv155_out_mfma(
     }
 }
 
+// ---- the same conv walking y: the f32 route ------------------------------
+// Same GEMM, B fragments, accumulation order and shifted sum as
+// k_conv155_out_mfma (the two are bit-equal), tiled the other way. A wave
+// owns CY_XO = 12 output positions (16 staged, x' = xo-2 .. xo+13: tiles
+// overlap by the 4-column halo, so a wave needs no neighbour and the
+// kernel has no workgroup barrier) and a y segment of CY_YS rows of one
+// (n, z) plane, and walks the input rows y0-2 .. y0+YS+1 in order. Input
+// row r is tap dy of output row r-dy: five rolling accumulator chains are
+// live, row r feeds all five (35 MFMAs on 7 A fragments), and output row
+// r-4 is finished after it. The input is read (YS+4)/YS = 1.125x in y and
+// 16/12 in x (neighbouring waves of a workgroup, L1/L2 hits) and nothing
+// but one row tile is ever staged: 22 tiles per row at W = 256 against
+// the fixed tiles' 18, 16/12 more MFMAs for no barrier.
+// A row's 16 x 28 input values are one contiguous 1792-byte run: each
+// lane loads two 16-byte pieces of it, a row ahead, and the run is staged
+// in wave-private LDS, where lane (i, kk) reads in[x'+i][4s+kk] as
+// s_a[i*28 + 4s + kk], conflict-free. (Taking the fragments straight from
+// global, 7 dword loads per lane that each touch 16 separate 16-byte
+// segments, was load-issue-bound: 1.36 ms against 1.05 ms this way and
+// 1.26 ms for the fixed tiles, profiles/conv_in_mfma.json.)
+// A finished row is bounced through wave-private LDS ([j][x'], 20-dword j
+// stride); lanes 0..8 each sum 4 of the tile's 36 contiguous outputs, in
+// the fixed-tile kernel's order, and store 16 bytes (one output per lane
+// and scalar stores when W % 4 != 0 or `out` is misaligned). The stores
+// are issued a row later, ahead of the next batch of loads, so the wait
+// for those loads never waits for a young store (loads and stores share
+// vmcnt). 113 VGPRs, 12 KB of LDS per workgroup: 4 waves per SIMD.
+// f32 only: in bf16 the fixed tiles hold 4 workgroups per CU and stay
+// faster (2.85 ms against 3.39 ms at 24x32x256x256).
+constexpr int CY_YS = 32;   // output rows per wave
+constexpr int CY_XO = 12;   // output positions per wave (16 staged)
+constexpr int CY_NW = 4;    // waves per workgroup, independent
+constexpr int CY_PS = 20;   // P bounce: dwords between j rows
+
+__global__ __launch_bounds__(CY_NW * 64, 4) void k_conv155_out_ywalk(
+    const float* __restrict__ in, const float* __restrict__ wfrag,
+    const float* __restrict__ bias, float* __restrict__ out, int H, int W,
+    int nxg, int nseg, int vec_ok) {
+    constexpr int CC = 28, C4 = CC / 4;
+    __shared__ __attribute__((aligned(16))) float s_bounce[CY_NW][16 * CY_PS];
+    __shared__ __attribute__((aligned(16))) float s_tile[CY_NW][16 * CC];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int ai = lane & 15, akk = lane >> 4;
+    const int xg = (int)blockIdx.x % nxg;
+    const int rest = (int)blockIdx.x / nxg;
+    const int y0 = (rest % nseg) * CY_YS;
+    const long long plane = (long long)(rest / nseg) * H;
+    const int xo = (xg * CY_NW + wave) * CY_XO;
+    if (xo >= W) return;
+    const int nout = min(CY_XO, W - xo);
+    const int ys = min(CY_YS, H - y0);
+    float* s_p = s_bounce[wave];
+    float* s_a = s_tile[wave];
+
+    float b[35];
+#pragma unroll
+    for (int s = 0; s < 35; ++s) b[s] = wfrag[s * 64 + lane];
+    float bk[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) bk[k] = bias ? bias[k] : 0.f;
+
+    // the tile's 16 x 28 input values of a row are one contiguous run of
+    // 112 four-channel pieces: lane l loads pieces l and l + 64 (clamped:
+    // lanes >= 48 repeat piece 111), coalesced, and the run is staged as it
+    // is in wave-private LDS, where lane (i, kk) reads its A fragments
+    // s_a[i*28 + 4s + kk] without bank conflicts
+    unsigned poff[2];
+    bool pok[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int f = min(lane + 64 * j, 16 * C4 - 1);
+        const int gx = xo - 2 + f / C4;
+        pok[j] = gx >= 0 && gx < W;
+        poff[j] = min(max(gx, 0), W - 1) * CC + 4 * (f % C4);
+    }
+    auto a_loads = [&](int r, co_f32x4 (&v)[2]) {
+        const int cy = min(max(y0 - 2 + r, 0), H - 1);
+        const float* ip = in + (plane + cy) * W * CC;
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            v[j] = *reinterpret_cast<const co_f32x4*>(ip + poff[j]);
+    };
+    auto a_stage = [&](const co_f32x4 (&v)[2]) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            co_f32x4 w;
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                w[e] = pok[j] ? v[j][e] : 0.f;
+            *reinterpret_cast<co_f32x4*>(
+                &s_a[4 * min(lane + 64 * j, 16 * C4 - 1)]) = w;
+        }
+        __builtin_amdgcn_wave_barrier();
+    };
+    // P[x + dx][dx*3 + k] summed onto the bias, dx ascending
+    auto outval = [&](int e) {
+        const int x = e / 3, k = e - 3 * x;
+        float o = k == 0 ? bk[0] : (k == 1 ? bk[1] : bk[2]);
+#pragma unroll
+        for (int dx = 0; dx < 5; ++dx)
+            o += s_p[(dx * 3 + k) * CY_PS + x + dx];
+        return o;
+    };
+    // a finished row: D[row = akk*4 + reg][col = ai] -> s_p[j][x'], then
+    // this lane's outputs (4 consecutive of the 36, or one) in registers
+    auto finish = [&](const co_f32x4& p) {
+        *reinterpret_cast<co_f32x4*>(&s_p[ai * CY_PS + akk * 4]) = p;
+        __builtin_amdgcn_wave_barrier();
+        co_f32x4 o = co_f32x4{0.f, 0.f, 0.f, 0.f};
+        if (vec_ok) {
+            if (4 * lane < 3 * nout) {
+#pragma unroll
+                for (int m = 0; m < 4; ++m) o[m] = outval(4 * lane + m);
+            }
+        } else if (lane < 3 * nout) {
+            o[0] = outval(lane);
+        }
+        __builtin_amdgcn_wave_barrier();  // s_p is rewritten next row
+        return o;
+    };
+    // ... and its stores, issued a row later: ahead of the next batch of
+    // loads, so that the wait for those loads never waits for a young store
+    auto put = [&](int yl, const co_f32x4& o) {
+        float* op = out + ((plane + y0 + yl) * W + xo) * 3LL;
+        if (vec_ok) {
+            if (4 * lane < 3 * nout)
+                reinterpret_cast<co_f32x4*>(op)[lane] = o;
+        } else if (lane < 3 * nout) {
+            op[lane] = o[0];
+        }
+    };
+
+    // acc[q] belongs to output row r - 4 + q while input row r is walked:
+    // row r is tap dy of acc[4 - dy]
+    co_f32x4 acc[5];
+#pragma unroll
+    for (int q = 0; q < 5; ++q) acc[q] = co_f32x4{0.f, 0.f, 0.f, 0.f};
+    const int nrow = ys + 4;  // input rows walked
+    float a[C4];
+    co_f32x4 an[2];
+    co_f32x4 pend = co_f32x4{0.f, 0.f, 0.f, 0.f};
+    a_loads(0, an);
+    a_stage(an);
+#pragma unroll 1
+    for (int r = 0; r < nrow; ++r) {
+        // the finished row's stores go out ahead of the next row's loads:
+        // the wait for those loads (at a_stage, a row of MFMAs later) then
+        // finds the store older still
+        if (r >= 5) put(r - 5, pend);
+        a_loads(min(r + 1, nrow - 1), an);
+#pragma unroll
+        for (int s = 0; s < C4; ++s) a[s] = s_a[ai * CC + 4 * s + akk];
+        __builtin_amdgcn_wave_barrier();
+        const int gy = y0 - 2 + r;
+        if (r >= 4 && r < ys && gy < H) {  // all five taps live
+#pragma unroll
+            for (int s = 0; s < C4; ++s)
+#pragma unroll
+                for (int dy = 0; dy < 5; ++dy)
+                    acc[4 - dy] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                        a[s], b[dy * C4 + s], acc[4 - dy], 0, 0, 0);
+        } else if (gy >= 0 && gy < H) {  // roll-in and roll-out
+#pragma unroll
+            for (int dy = 0; dy < 5; ++dy) {
+                if (r - dy < 0 || r - dy >= ys) continue;
+#pragma unroll
+                for (int s = 0; s < C4; ++s)
+                    acc[4 - dy] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                        a[s], b[dy * C4 + s], acc[4 - dy], 0, 0, 0);
+            }
+        }
+        if (r >= 4) pend = finish(acc[0]);  // output row r - 4 is done
+        a_stage(an);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[q] = acc[q + 1];
+        acc[4] = co_f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    put(ys - 1, pend);
+}
+
 // ---- one-pass epilogue for the convs left on MIOpen ----------------------
 // y[v][k] = act(y[v][k] + bias[k] (+ res[v][k])), in place on an NDHWC f32
 // tensor: the bias pass, the residual add and the ELU that torch runs as
@@ -784,19 +1023,33 @@ extern "C" int cfx_conv155_out(cfx_ctx* ctx, const void* in,
         g_err = "cfx_conv155_out: N * D <= 65535 supported";
         return -1;
     }
+    if (!is_bf16 && (long long)N * D * ((H + CY_YS - 1) / CY_YS) *
+                            ((W + CY_NW * CY_XO - 1) / (CY_NW * CY_XO)) >
+                        0x7fffffffLL) {
+        g_err = "cfx_conv155_out: too many workgroups for one grid axis";
+        return -1;
+    }
     hipEvent_t e0;
     if (prof_begin(ctx, &e0)) return -1;
     dim3 grid((W + CO_S - 1) / CO_S, (H + CO_R - 1) / CO_R,
               (unsigned)(N * D));
     const int vec_ok = W % 4 == 0 && ((size_t)out & 15) == 0;
-    if (is_bf16)
+    if (is_bf16) {
+        // bf16 stays on the fixed tiles: 4 workgroups per CU there, and
+        // the y-walk measured slower (profiles/conv_in_mfma.json)
         hipLaunchKernelGGL((k_conv155_out_mfma<cfx_bf16>), grid, dim3(256),
                            0, ctx->stream, (const cfx_bf16*)in, wfrag, bias,
                            (cfx_bf16*)out, H, W, vec_ok);
-    else
-        hipLaunchKernelGGL((k_conv155_out_mfma<float>), grid, dim3(256), 0,
-                           ctx->stream, (const float*)in, wfrag, bias,
-                           (float*)out, H, W, vec_ok);
+    } else {
+        const int nxg = (W + CY_NW * CY_XO - 1) / (CY_NW * CY_XO);
+        const int nseg = (H + CY_YS - 1) / CY_YS;
+        const long long nwg = (long long)N * D * nseg * nxg;
+        if (nwg > 0)
+            hipLaunchKernelGGL(k_conv155_out_ywalk, dim3((unsigned)nwg),
+                               dim3(CY_NW * 64), 0, ctx->stream,
+                               (const float*)in, wfrag, bias, (float*)out, H,
+                               W, nxg, nseg, vec_ok);
+    }
     CFX_CHECK(hipGetLastError());
     double flops = 2.0 * 25.0 * C * K * (double)N * D * H * W;
     if (prof_end(ctx, e0, CFX_K_CONV_STREAM, flops)) return -1;
@@ -810,30 +1063,34 @@ extern "C" int cfx_conv155_c1(cfx_ctx* ctx, const void* in, const void* wgt,
         g_err = "cfx_conv155_c1: K <= 32 supported";
         return -1;
     }
-    constexpr int XI = 256;
-    dim3 grid((W + XI - 1) / XI, H, (unsigned)(N * D));
+    if (K < 1 || N < 0 || D < 0 || H < 1 || W < 1) {
+        g_err = "cfx_conv155_c1: K >= 1, N, D >= 0, H, W >= 1";
+        return -1;
+    }
+    // one flat grid axis over (plane, row group, strip): no 65535 limit
+    const int nstrips = (W + CI_S - 1) / CI_S;
+    const int nrows = (H + CI_R - 1) / CI_R;
+    const long long nwg = (long long)N * D * nrows * nstrips;
+    if (nwg > 0x7fffffffLL) {
+        g_err = "cfx_conv155_c1: N * D * ceil(H/8) * ceil(W/64) < 2^31 "
+                "supported";
+        return -1;
+    }
+    if (nwg == 0) return 0;
+    const int vec_ok = K % 4 == 0 && ((size_t)out & 15) == 0;
     hipEvent_t e0;
     if (prof_begin(ctx, &e0)) return -1;
-    if (is_bf16 && K == 28)
-        hipLaunchKernelGGL((k_conv155_c1<cfx_bf16, XI, 28>), grid,
-                           dim3(XI), 0, ctx->stream, (const cfx_bf16*)in,
-                           (const cfx_bf16*)wgt, bias, (cfx_bf16*)out, N,
-                           D, H, W, K);
-    else if (is_bf16)
-        hipLaunchKernelGGL((k_conv155_c1<cfx_bf16, XI, 0>), grid,
-                           dim3(XI), 0, ctx->stream, (const cfx_bf16*)in,
-                           (const cfx_bf16*)wgt, bias, (cfx_bf16*)out, N,
-                           D, H, W, K);
-    else if (K == 28)
-        hipLaunchKernelGGL((k_conv155_c1<float, XI, 28>), grid, dim3(XI),
-                           0, ctx->stream, (const float*)in,
-                           (const float*)wgt, bias, (float*)out, N, D, H,
-                           W, K);
+    if (is_bf16)
+        hipLaunchKernelGGL((k_conv155_in_mfma<cfx_bf16>),
+                           dim3((unsigned)nwg), dim3(CI_NW * 64), 0,
+                           ctx->stream, (const cfx_bf16*)in,
+                           (const cfx_bf16*)wgt, bias, (cfx_bf16*)out, H, W,
+                           K, nstrips, nrows, vec_ok);
     else
-        hipLaunchKernelGGL((k_conv155_c1<float, XI, 0>), grid, dim3(XI),
-                           0, ctx->stream, (const float*)in,
-                           (const float*)wgt, bias, (float*)out, N, D, H,
-                           W, K);
+        hipLaunchKernelGGL((k_conv155_in_mfma<float>), dim3((unsigned)nwg),
+                           dim3(CI_NW * 64), 0, ctx->stream,
+                           (const float*)in, (const float*)wgt, bias,
+                           (float*)out, H, W, K, nstrips, nrows, vec_ok);
     CFX_CHECK(hipGetLastError());
     double flops = 2.0 * 25.0 * K * (double)N * D * H * W;
     if (prof_end(ctx, e0, CFX_K_CONV_STREAM, flops)) return -1;

@@ -353,8 +353,13 @@ class CfxDownConv3d(_CfxConv):
 class CfxConvIn155(_CfxConv):
     """Drop-in for nn.Conv3d(1, K, (1,5,5), padding=(0,2,2)) — the RSUNet
     input conv. MIOpen's implicit GEMM degenerates on the single input
-    channel (measured 38.8 ms bf16 / 6.8 ms f32 per batch-24 launch vs
-    ~0.5 ms algorithmic); csrc/updown.hip runs it as a 2-D stencil."""
+    channel (measured 38.8 ms bf16 / 6.8 ms f32 per batch-24 launch);
+    csrc/updown.hip runs it as a GEMM on the f32 matrix cores (16 x of a
+    row by the 25 taps, K <= 32 outputs; f32 accumulation, bf16 rounded
+    once at the store): f32 12x20x256^2 0.405 ms, bf16 24x32x256^2
+    1.02 ms, against 1.04 / 2.08 ms for the VALU stencil it replaces
+    (profiles/conv_in_mfma.json). `wpack` is the plain [K][25] weight in
+    the compute dtype; the kernel gathers its B fragments from it."""
 
     def __init__(self, conv: nn.Conv3d, device_index: int = 0,
                  bf16: bool = False):
@@ -380,7 +385,9 @@ class CfxConvOut155(_CfxConv):
     tiny K (measured 38.6 ms per batch-24 launch vs 2.85 ms here;
     f32 at batch 12 x 20: 6.76 ms vs 1.29 ms, profiles/convout_mfma.json).
     28 -> 3 only: the five x-taps are folded into the MFMA's output
-    dimension (csrc/updown.hip)."""
+    dimension (csrc/updown.hip). f32 walks y with five rolling
+    accumulators (1.05 ms, profiles/conv_in_mfma.json); bf16 runs the
+    fixed 6-row tiles. Both use the same `wpack` and summation order."""
 
     def __init__(self, conv: nn.Conv3d, device_index: int = 0,
                  bf16: bool = False):

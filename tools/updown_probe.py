@@ -11,12 +11,19 @@ to gpurun_out/updown_probe.json."""
 # `--miopen-block OUT.json` times one C=48 ResBlock at 12 x 20 x 64^2 as
 # torch runs it (MIOpen conv + bias pass, ELU pass, add pass) against
 # CfxMiopenResBlock (bias-free conv + one in-place epilogue), alternated.
+# `--conv155 OUT.json [--tree DIR]` times the two (1,5,5) convs alone at
+# 12x20x256x256 f32 and 24x32x256x256 bf16, the package taken from DIR
+# (another checkout, built) when given: one process per tree, alternated
+# by the caller, for a kernel-alone A/B.
 import json
 import os
 import sys
 import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+_TREE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if '--tree' in sys.argv:
+    _TREE = os.path.abspath(sys.argv[sys.argv.index('--tree') + 1])
+sys.path.insert(0, _TREE)
 import torch
 import torch.nn as nn
 
@@ -127,6 +134,38 @@ def probe_conv155_out(N, D, H, W, bf16):
     print(name, RES[name], flush=True)
 
 
+def probe_conv155_alone(path, rounds=3):
+    """conv_in (1 -> 28) and conv_out (28 -> 3) alone, drained-queue timing;
+    GB/s is (in + out bytes) / best time."""
+    res = {'tree': _TREE}
+    for N, D, bf16 in ((12, 20, False), (24, 32, True)):
+        dt = torch.bfloat16 if bf16 else torch.float32
+        for name, C, K, cls in (('conv_in', 1, 28, CfxConvIn155),
+                                ('conv_out', 28, 3, CfxConvOut155)):
+            torch.manual_seed(0)
+            conv = nn.Conv3d(C, K, (1, 5, 5), padding=(0, 2, 2)).cuda()
+            repl = cls(conv, 0, bf16=bf16).cuda()
+            x = torch.randn(N, C, D, 256, 256, device='cuda').to(dt) \
+                .contiguous(memory_format=cl)
+            nbytes = x.element_size() * N * D * 256 * 256 * (C + K)
+            with torch.no_grad():
+                ms = [timeit(lambda: repl(x), 20) * 1e3
+                      for _ in range(rounds)]
+                # a small slab against torch, as a sanity check of the run
+                want = conv.to(dt)(x[:1, :, :2]).float()
+                err = (repl(x[:1, :, :2].contiguous(memory_format=cl))
+                       .float() - want).abs().max().item()
+            key = f'{name}_{"bf16" if bf16 else "f32"}_{N}x{D}x256x256'
+            res[key] = {'ms': ms, 'bytes_in_out': nbytes,
+                        'gbps': nbytes / min(ms) / 1e6, 'max_err': err}
+            print(key, res[key], flush=True)
+            del x, repl, conv
+            torch.cuda.empty_cache()
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, 'w') as f:
+        json.dump(res, f, indent=1)
+
+
 def probe_upskip(path, rounds=3):
     """f32 up-conv + skip-add at 12 x 20 x {128^2, 64^2, 32^2}; TB/s is
     (in + skip + out bytes) / time, the traffic the fused result needs."""
@@ -219,6 +258,9 @@ def probe_miopen_block(path, rounds=4):
 def main():
     if len(sys.argv) > 2 and sys.argv[1] == '--upskip':
         probe_upskip(sys.argv[2])
+        return
+    if len(sys.argv) > 2 and sys.argv[1] == '--conv155':
+        probe_conv155_alone(sys.argv[2])
         return
     if len(sys.argv) > 2 and sys.argv[1] == '--miopen-block':
         probe_miopen_block(sys.argv[2])
