@@ -245,26 +245,20 @@ int run_cc(cfx_ctx* ctx, P pred, int elem_bytes, const int dims[3],
         g_err = "connectivity must be 6, 18 or 26";
         return -1;
     }
-    hipEvent_t e0;
-    if (prof_begin(ctx, &e0)) return -1;
-    hipLaunchKernelGGL(k_cc_init<P>, dim3(grid_for(n, 256)), dim3(256), 0,
-                       ctx->stream, pred, labels, n);
-    hipLaunchKernelGGL(k_cc_merge<P>, dim3(grid_for(n, 256)), dim3(256), 0,
-                       ctx->stream, pred, labels, D, H, W, ndirs);
-    hipLaunchKernelGGL(k_cc_compress<P>, dim3(grid_for(n, 256)), dim3(256),
-                       0, ctx->stream, pred, labels, n);
-
-    if (cc_rank_roots(ctx, labels, n, scratch, n_components)) {
-        prof_drop(ctx, e0);
-        return -1;
-    }
-    hipLaunchKernelGGL(k_cc_final<P>, dim3(grid_for(n, 256)), dim3(256), 0,
-                       ctx->stream, pred, labels, scratch, labels, n);
-    CFX_CHECK(hipGetLastError());
     // algorithmic bytes: voxel reads x3 + parent RMW passes + final gather
     double bytes = (double)n * (3.0 * elem_bytes + 4.0 * 6.0);
-    if (prof_end(ctx, e0, CFX_K_CC, bytes)) return -1;
-    return 0;
+    return cfx_timed(ctx, CFX_K_CC, bytes, [&] {
+        hipLaunchKernelGGL(k_cc_init<P>, dim3(grid_for(n, 256)), dim3(256),
+                           0, ctx->stream, pred, labels, n);
+        hipLaunchKernelGGL(k_cc_merge<P>, dim3(grid_for(n, 256)), dim3(256),
+                           0, ctx->stream, pred, labels, D, H, W, ndirs);
+        hipLaunchKernelGGL(k_cc_compress<P>, dim3(grid_for(n, 256)),
+                           dim3(256), 0, ctx->stream, pred, labels, n);
+        if (cc_rank_roots(ctx, labels, n, scratch, n_components)) return -1;
+        hipLaunchKernelGGL(k_cc_final<P>, dim3(grid_for(n, 256)), dim3(256),
+                           0, ctx->stream, pred, labels, scratch, labels, n);
+        return 0;
+    });
 }
 
 }  // namespace

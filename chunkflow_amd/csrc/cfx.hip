@@ -75,26 +75,38 @@ extern "C" int cfx_sync(cfx_ctx* ctx) {
 }
 
 // profiling helpers ---------------------------------------------------------
-int prof_begin(cfx_ctx* ctx, hipEvent_t* e0) {
-    if (!ctx->profile) return 0;
-    CFX_CHECK(hipEventCreate(e0));
-    CFX_CHECK(hipEventRecord(*e0, ctx->stream));
+// The two halves of cfx_timed (cfx_internal.h) with profiling on. An event
+// that was created and does not reach ctx->pending is destroyed here,
+// whichever step failed; g_err stays as the failing step set it.
+int timed_open(cfx_ctx* ctx, hipEvent_t* e) {
+    CFX_CHECK(hipEventCreate(e));
+    hipError_t err = hipEventRecord(*e, ctx->stream);
+    if (err != hipSuccess) {
+        g_err = std::string("hipEventRecord: ") + hipGetErrorString(err);
+        (void)hipEventDestroy(*e);
+        return -1;
+    }
     return 0;
 }
 
-int prof_end(cfx_ctx* ctx, hipEvent_t e0, int kid, double bytes) {
-    if (!ctx->profile) return 0;
+// rc is what the region's enqueue() returned
+int timed_close(cfx_ctx* ctx, hipEvent_t e0, int rc, int kid, double work) {
     hipEvent_t e1;
-    CFX_CHECK(hipEventCreate(&e1));
-    CFX_CHECK(hipEventRecord(e1, ctx->stream));
-    ctx->pending.push_back({e0, e1, kid, bytes});
+    if (rc == 0) {
+        hipError_t err = hipGetLastError();
+        if (err != hipSuccess) {
+            g_err = std::string("hipGetLastError(): ") +
+                    hipGetErrorString(err);
+            rc = -1;
+        }
+    }
+    if (rc == 0) rc = timed_open(ctx, &e1);  // the end event
+    if (rc != 0) {
+        (void)hipEventDestroy(e0);
+        return rc;
+    }
+    ctx->pending.push_back({e0, e1, kid, work});
     return 0;
-}
-
-// a timed region that fails between prof_begin and prof_end gives its
-// start event back
-void prof_drop(cfx_ctx* ctx, hipEvent_t e0) {
-    if (ctx->profile) (void)hipEventDestroy(e0);
 }
 
 extern "C" int cfx_profile_enable(cfx_ctx* ctx, int enable) {
@@ -189,26 +201,27 @@ __global__ void k_u8_to_f32_tail(const unsigned char* __restrict__ in,
 
 static int u8_to_f32(cfx_ctx* ctx, const unsigned char* in, float* out,
                      long long n, float divisor, float bias, int kid) {
-    hipEvent_t e0;
-    if (prof_begin(ctx, &e0)) return -1;
-    int threads = 256;
-    // uchar4 -> float4 body only from a 4-byte source and 16-byte destination
-    long long n4 = aligned_to(in, 4) && aligned_to(out, 16) ? n / 4 : 0;
-    if (n4 > 0) {
-        long long want = (n4 + threads - 1) / threads;
-        int blocks = (int)std::min<long long>(want, 8192);
-        hipLaunchKernelGGL(k_u8_to_f32, dim3(blocks), dim3(threads), 0,
-                           ctx->stream, in, out, n4, divisor, bias);
-    }
-    if (n4 * 4 < n) {
-        long long want = (n - n4 * 4 + threads - 1) / threads;
-        int blocks = (int)std::min<long long>(want, 8192);
-        hipLaunchKernelGGL(k_u8_to_f32_tail, dim3(blocks), dim3(threads), 0,
-                           ctx->stream, in, out, n4 * 4, n, divisor, bias);
-    }
-    CFX_CHECK(hipGetLastError());
-    if (prof_end(ctx, e0, kid, (double)n * 5.0)) return -1;  // 1B read + 4B write
-    return 0;
+    // 1B read + 4B write
+    return cfx_timed(ctx, kid, (double)n * 5.0, [&] {
+        int threads = 256;
+        // uchar4 -> float4 body only from a 4-byte source and 16-byte
+        // destination
+        long long n4 = aligned_to(in, 4) && aligned_to(out, 16) ? n / 4 : 0;
+        if (n4 > 0) {
+            long long want = (n4 + threads - 1) / threads;
+            int blocks = (int)std::min<long long>(want, 8192);
+            hipLaunchKernelGGL(k_u8_to_f32, dim3(blocks), dim3(threads), 0,
+                               ctx->stream, in, out, n4, divisor, bias);
+        }
+        if (n4 * 4 < n) {
+            long long want = (n - n4 * 4 + threads - 1) / threads;
+            int blocks = (int)std::min<long long>(want, 8192);
+            hipLaunchKernelGGL(k_u8_to_f32_tail, dim3(blocks), dim3(threads),
+                               0, ctx->stream, in, out, n4 * 4, n, divisor,
+                               bias);
+        }
+        return 0;
+    });
 }
 
 extern "C" int cfx_normalize_intensity(cfx_ctx* ctx, const unsigned char* in,
@@ -306,22 +319,22 @@ extern "C" int cfx_extract_patches(cfx_ctx* ctx, const float* chunk,
             args.starts[i * 3 + 2] = starts_zyx[(base + i) * 3 + 2];
             vec = vec && (args.starts[i * 3 + 2] % 4 == 0);
         }
-        hipEvent_t e0;
-        if (prof_begin(ctx, &e0)) return -1;
         long long n_lines = (long long)n * channels * pz * py;
         long long n_groups = (n_lines + 1) / 2;  // G=2
         int blocks = (int)std::min<long long>((n_groups + 3) / 4, 8192);
-        if (vec)
-            hipLaunchKernelGGL(k_extract<true>, dim3(blocks), dim3(64, 4),
-                               0, ctx->stream, chunk, channels, D, H, W,
-                               args, pz, py, px, dst);
-        else
-            hipLaunchKernelGGL(k_extract<false>, dim3(blocks), dim3(64, 4),
-                               0, ctx->stream, chunk, channels, D, H, W,
-                               args, pz, py, px, dst);
-        CFX_CHECK(hipGetLastError());
         double bytes = (double)n * channels * pvox * 8.0;  // read + write f32
-        if (prof_end(ctx, e0, CFX_K_EXTRACT, bytes)) return -1;
+        int rc = cfx_timed(ctx, CFX_K_EXTRACT, bytes, [&] {
+            if (vec)
+                hipLaunchKernelGGL(k_extract<true>, dim3(blocks),
+                                   dim3(64, 4), 0, ctx->stream, chunk,
+                                   channels, D, H, W, args, pz, py, px, dst);
+            else
+                hipLaunchKernelGGL(k_extract<false>, dim3(blocks),
+                                   dim3(64, 4), 0, ctx->stream, chunk,
+                                   channels, D, H, W, args, pz, py, px, dst);
+            return 0;
+        });
+        if (rc) return rc;
     }
     return 0;
 }
@@ -553,25 +566,23 @@ static int blend_one(cfx_ctx* ctx, float* out, int C, const int out_dims[3],
     long long n_lines = (long long)C * r[0] * r[1];
     long long n_groups = (n_lines + 3) / 4;          // G=4 lines per group
     int blocks = (int)std::min<long long>((n_groups + 3) / 4, 8192);
-    hipEvent_t e0;
-    if (prof_begin(ctx, &e0)) return -1;
+    double rv = (double)r[0] * r[1] * r[2];
+    // algorithmic bytes: out read+write + patch read (per channel) + mask read
+    double bytes = rv * C * 12.0 + (mask ? rv * 4.0 : 0.0);
 #define CFX_LAUNCH_BLEND(V, M)                                              \
     hipLaunchKernelGGL((k_blend<V, M>), dim3(blocks), dim3(64, 4), 0,       \
                        ctx->stream, out, out_dims[0], out_dims[1],          \
                        out_dims[2], patch, patch_dims[0], patch_dims[1],    \
                        patch_dims[2], mask, C, d0[0], d0[1], d0[2], p0[0],  \
                        p0[1], p0[2], r[0], r[1], r[2])
-    if (vec && mask) CFX_LAUNCH_BLEND(true, true);
-    else if (vec) CFX_LAUNCH_BLEND(true, false);
-    else if (mask) CFX_LAUNCH_BLEND(false, true);
-    else CFX_LAUNCH_BLEND(false, false);
+    return cfx_timed(ctx, CFX_K_BLEND, bytes, [&] {
+        if (vec && mask) CFX_LAUNCH_BLEND(true, true);
+        else if (vec) CFX_LAUNCH_BLEND(true, false);
+        else if (mask) CFX_LAUNCH_BLEND(false, true);
+        else CFX_LAUNCH_BLEND(false, false);
+        return 0;
+    });
 #undef CFX_LAUNCH_BLEND
-    CFX_CHECK(hipGetLastError());
-    double rv = (double)r[0] * r[1] * r[2];
-    // algorithmic bytes: out read+write + patch read (per channel) + mask read
-    double bytes = rv * C * 12.0 + (mask ? rv * 4.0 : 0.0);
-    if (prof_end(ctx, e0, CFX_K_BLEND, bytes)) return -1;
-    return 0;
 }
 
 extern "C" int cfx_blend_accumulate(cfx_ctx* ctx, float* out, int channels,
@@ -637,8 +648,6 @@ extern "C" int cfx_blend_batch(cfx_ctx* ctx, float* out, int channels,
         long long n_lines = a.line_start[a.n];
         long long n_groups = (n_lines + env_g - 1) / env_g;
         int blocks = (int)std::min<long long>((n_groups + 3) / 4, 8192);
-        hipEvent_t e0;
-        if (prof_begin(ctx, &e0)) return -1;
 #define CFX_LAUNCH_BB(G, V, M, NT)                                           \
     hipLaunchKernelGGL((k_blend_batch<G, V, M, NT>), dim3(blocks),           \
                        dim3(64, 4), 0, ctx->stream, out, out_dims[0],        \
@@ -654,13 +663,15 @@ extern "C" int cfx_blend_batch(cfx_ctx* ctx, float* out, int channels,
         else if (mask) CFX_LAUNCH_BB(G, false, true, false);                 \
         else CFX_LAUNCH_BB(G, false, false, false);                          \
     } while (0)
-        if (env_g == 2) CFX_DISPATCH_G(2);
-        else if (env_g == 8) CFX_DISPATCH_G(8);
-        else CFX_DISPATCH_G(4);
+        int rc = cfx_timed(ctx, CFX_K_BLEND, bytes, [&] {
+            if (env_g == 2) CFX_DISPATCH_G(2);
+            else if (env_g == 8) CFX_DISPATCH_G(8);
+            else CFX_DISPATCH_G(4);
+            return 0;
+        });
 #undef CFX_DISPATCH_G
 #undef CFX_LAUNCH_BB
-        CFX_CHECK(hipGetLastError());
-        if (prof_end(ctx, e0, CFX_K_BLEND, bytes)) return -1;
+        if (rc) return rc;
     }
     return 0;
 }
@@ -675,16 +686,14 @@ __global__ void k_reciprocal(float* __restrict__ buf, long long n) {
 }
 
 extern "C" int cfx_reciprocal(cfx_ctx* ctx, float* buf, long long n) {
-    hipEvent_t e0;
-    if (prof_begin(ctx, &e0)) return -1;
     int threads = 256;
     long long want = (n + threads - 1) / threads;
     int blocks = (int)std::min<long long>(want, 8192);
-    hipLaunchKernelGGL(k_reciprocal, dim3(blocks), dim3(threads), 0,
-                       ctx->stream, buf, n);
-    CFX_CHECK(hipGetLastError());
-    if (prof_end(ctx, e0, CFX_K_RECIPROCAL, (double)n * 8.0)) return -1;
-    return 0;
+    return cfx_timed(ctx, CFX_K_RECIPROCAL, (double)n * 8.0, [&] {
+        hipLaunchKernelGGL(k_reciprocal, dim3(blocks), dim3(threads), 0,
+                           ctx->stream, buf, n);
+        return 0;
+    });
 }
 
 extern "C" int cfx_build_chunk_mask(cfx_ctx* ctx, float* mask_out,
@@ -787,32 +796,31 @@ static bool maskmul_vec(const float* out, const float* mask,
 static int multiply_mask_impl(cfx_ctx* ctx, float* out, const float* mask,
                               int channels, long long n_voxels,
                               bool with_max) {
-    hipEvent_t e0;
-    if (prof_begin(ctx, &e0)) return -1;
-    int threads = 256;
-    if (maskmul_vec(out, mask, n_voxels)) {
-        long long n4 = n_voxels / 4;
-        long long want = (n4 + threads * 2 - 1) / (threads * 2);
-        int blocks = (int)std::min<long long>(want, 8192);
-        if (with_max)
-            hipLaunchKernelGGL(k_maskmul<true>, dim3(blocks), dim3(threads),
-                               0, ctx->stream, out, mask, n4, channels, n4,
-                               ctx->dev_max);
-        else
-            hipLaunchKernelGGL(k_maskmul<false>, dim3(blocks), dim3(threads),
-                               0, ctx->stream, out, mask, n4, channels, n4,
-                               nullptr);
-    } else {
-        long long want = (n_voxels + threads - 1) / threads;
-        int blocks = (int)std::min<long long>(want, 8192);
-        hipLaunchKernelGGL(k_maskmul_scalar, dim3(blocks), dim3(threads), 0,
-                           ctx->stream, out, mask, n_voxels, channels);
-        with_max = false;  // caller falls back to cfx_max
-    }
-    CFX_CHECK(hipGetLastError());
     double bytes = (double)n_voxels * (channels * 8.0 + 4.0);
-    if (prof_end(ctx, e0, CFX_K_MASKMUL, bytes)) return -1;
-    return 0;
+    return cfx_timed(ctx, CFX_K_MASKMUL, bytes, [&] {
+        int threads = 256;
+        if (maskmul_vec(out, mask, n_voxels)) {
+            long long n4 = n_voxels / 4;
+            long long want = (n4 + threads * 2 - 1) / (threads * 2);
+            int blocks = (int)std::min<long long>(want, 8192);
+            if (with_max)
+                hipLaunchKernelGGL(k_maskmul<true>, dim3(blocks),
+                                   dim3(threads), 0, ctx->stream, out, mask,
+                                   n4, channels, n4, ctx->dev_max);
+            else
+                hipLaunchKernelGGL(k_maskmul<false>, dim3(blocks),
+                                   dim3(threads), 0, ctx->stream, out, mask,
+                                   n4, channels, n4, nullptr);
+        } else {
+            // no fused max here: cfx_multiply_mask_max tests maskmul_vec
+            // itself and sends the caller to cfx_max
+            long long want = (n_voxels + threads - 1) / threads;
+            int blocks = (int)std::min<long long>(want, 8192);
+            hipLaunchKernelGGL(k_maskmul_scalar, dim3(blocks), dim3(threads),
+                               0, ctx->stream, out, mask, n_voxels, channels);
+        }
+        return 0;
+    });
 }
 
 extern "C" int cfx_multiply_mask(cfx_ctx* ctx, float* out, const float* mask,
@@ -904,15 +912,15 @@ extern "C" int cfx_max(cfx_ctx* ctx, const float* buf, long long n,
     unsigned int init = f32_ord(-INFINITY);
     CFX_CHECK(hipMemcpyAsync(ctx->dev_max, &init, sizeof(init),
                              hipMemcpyHostToDevice, ctx->stream));
-    hipEvent_t e0;
-    if (prof_begin(ctx, &e0)) return -1;
     int threads = 256;
     long long want = (n + threads - 1) / threads;
     int blocks = (int)std::min<long long>(want, 4096);
-    hipLaunchKernelGGL(k_max, dim3(blocks), dim3(threads), 0, ctx->stream,
-                       buf, n, ctx->dev_max);
-    CFX_CHECK(hipGetLastError());
-    if (prof_end(ctx, e0, CFX_K_MAX, (double)n * 4.0)) return -1;
+    int rc = cfx_timed(ctx, CFX_K_MAX, (double)n * 4.0, [&] {
+        hipLaunchKernelGGL(k_max, dim3(blocks), dim3(threads), 0,
+                           ctx->stream, buf, n, ctx->dev_max);
+        return 0;
+    });
+    if (rc) return rc;
     unsigned int out;
     CFX_CHECK(hipMemcpyAsync(&out, ctx->dev_max, sizeof(out),
                              hipMemcpyDeviceToHost, ctx->stream));
@@ -967,20 +975,18 @@ extern "C" int cfx_crop_margin(cfx_ctx* ctx, const float* in, float* out,
                aligned_to(in, 16) && aligned_to(out, 16);
     long long n_lines = (long long)channels * oD * oH;
     int blocks = (int)std::min<long long>((n_lines + 3) / 4, 8192);
-    hipEvent_t e0;
-    if (prof_begin(ctx, &e0)) return -1;
-    if (vec)
-        hipLaunchKernelGGL(k_crop<true>, dim3(blocks), dim3(64, 4), 0,
-                           ctx->stream, in, D, H, W, out, channels, oD, oH,
-                           oW, margins[0], margins[1], margins[2]);
-    else
-        hipLaunchKernelGGL(k_crop<false>, dim3(blocks), dim3(64, 4), 0,
-                           ctx->stream, in, D, H, W, out, channels, oD, oH,
-                           oW, margins[0], margins[1], margins[2]);
-    CFX_CHECK(hipGetLastError());
     double bytes = (double)channels * oD * oH * oW * 8.0;
-    if (prof_end(ctx, e0, CFX_K_CROP, bytes)) return -1;
-    return 0;
+    return cfx_timed(ctx, CFX_K_CROP, bytes, [&] {
+        if (vec)
+            hipLaunchKernelGGL(k_crop<true>, dim3(blocks), dim3(64, 4), 0,
+                               ctx->stream, in, D, H, W, out, channels, oD,
+                               oH, oW, margins[0], margins[1], margins[2]);
+        else
+            hipLaunchKernelGGL(k_crop<false>, dim3(blocks), dim3(64, 4), 0,
+                               ctx->stream, in, D, H, W, out, channels, oD,
+                               oH, oW, margins[0], margins[1], margins[2]);
+        return 0;
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -1005,17 +1011,15 @@ extern "C" int cfx_mask_using_last_channel(cfx_ctx* ctx, const float* in,
                                            float threshold) {
     long long n = (long long)dims[0] * dims[1] * dims[2];
     int cout = channels - 1;
-    hipEvent_t e0;
-    if (prof_begin(ctx, &e0)) return -1;
     int threads = 256;
     long long want = (n + threads - 1) / threads;
     int blocks = (int)std::min<long long>(want, 8192);
-    hipLaunchKernelGGL(k_myelin, dim3(blocks), dim3(threads), 0, ctx->stream,
-                       in, out, n, cout, threshold);
-    CFX_CHECK(hipGetLastError());
     double bytes = (double)n * (channels + cout) * 4.0;
-    if (prof_end(ctx, e0, CFX_K_MYELIN, bytes)) return -1;
-    return 0;
+    return cfx_timed(ctx, CFX_K_MYELIN, bytes, [&] {
+        hipLaunchKernelGGL(k_myelin, dim3(blocks), dim3(threads), 0,
+                           ctx->stream, in, out, n, cout, threshold);
+        return 0;
+    });
 }
 
 // ---------------------------------------------------------------------------

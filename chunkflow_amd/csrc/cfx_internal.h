@@ -42,8 +42,27 @@ extern thread_local std::string g_err;
         }                                                                    \
     } while (0)
 
-int prof_begin(cfx_ctx* ctx, hipEvent_t* e0);
-int prof_end(cfx_ctx* ctx, hipEvent_t e0, int kid, double bytes);
-void prof_drop(cfx_ctx* ctx, hipEvent_t e0);
+// the event half of cfx_timed (cfx.hip): an event created and recorded on
+// ctx->stream, and the end of a region, which owns e0 whatever happens
+int timed_open(cfx_ctx* ctx, hipEvent_t* e);
+int timed_close(cfx_ctx* ctx, hipEvent_t e0, int rc, int kid, double work);
+
+// One timed region: enqueue() launches on ctx->stream and returns 0, or
+// sets g_err and returns non-zero, which is passed on. A launch error
+// (hipGetLastError) fails the region too. With profiling on, a region that
+// succeeds pushes one ledger row {kid, work}; one that fails on any path
+// pushes none and leaves no event behind. With profiling off nothing but
+// enqueue() and the error check runs.
+template <typename F>
+int cfx_timed(cfx_ctx* ctx, int kid, double work, F&& enqueue) {
+    if (!ctx->profile) {
+        if (int rc = enqueue()) return rc;
+        CFX_CHECK(hipGetLastError());
+        return 0;
+    }
+    hipEvent_t e0;
+    if (timed_open(ctx, &e0)) return -1;
+    return timed_close(ctx, e0, enqueue(), kid, work);
+}
 
 #endif  // CFX_INTERNAL_H

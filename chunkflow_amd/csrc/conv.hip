@@ -269,33 +269,31 @@ extern "C" int cfx_conv3_ndhwc(cfx_ctx* ctx, const float* in,
         const int zb = (D + TZV - 1) / TZV;                                  \
         dim3 grid((W + TXV - 1) / TXV, (H + TYV - 1) / TYV,                  \
                   (unsigned)(N * zb));                                       \
-        hipEvent_t e0;                                                       \
-        if (prof_begin(ctx, &e0)) return -1;                                 \
         hipLaunchKernelGGL((k_conv3<CW, CW, TZV, TYV, TXV, TAPGV, NTH>),     \
                            grid, dim3(NTH), 0, ctx->stream, in, wgt, bias,   \
                            residual, out, N, D, H, W, do_elu);               \
-        CFX_CHECK(hipGetLastError());                                        \
-        double flops = 2.0 * 27.0 * CW * CW * (double)N * D * H * W;         \
-        if (prof_end(ctx, e0, CFX_K_CONV, flops)) return -1;                 \
-        break;                                                               \
+        return 0;                                                            \
     }
-    switch (C) {
-        // 28: slab 3*10*34*28*4 = 114 KB + wtile 10.5 KB (TZ1 TY8, 8 waves)
-        CFX_CONV_CASE(28, 1, 8, 32, 3, 512)
-        // 36: slab 3*10*34*36*4 = 147 KB + wtile 4.5 KB (TAPG 1)
-        CFX_CONV_CASE(36, 1, 8, 32, 1, 512)
-        // 48: slab 3*6*34*52*4 = 127 KB + wtile 9.2 KB (TZ1 TY4, 8 waves
-        // -> 1 m-tile per wave)
-        CFX_CONV_CASE(48, 1, 4, 32, 1, 512)
-        // 64: slab 3*6*18*68*4 = 86 KB + wtile 16.4 KB (TZ1 TY4 TX16;
-        // 8 waves x ... 1*4*1 = 4 tiles < 8 waves -> use 256 threads)
-        CFX_CONV_CASE(64, 2, 2, 16, 1, 256)
-        default:
-            g_err = "cfx_conv3_ndhwc: unsupported channel width";
-            return -1;
-    }
+    double flops = 2.0 * 27.0 * C * K * (double)N * D * H * W;
+    return cfx_timed(ctx, CFX_K_CONV, flops, [&] {
+        switch (C) {
+            // 28: slab 3*10*34*28*4 = 114 KB + wtile 10.5 KB (TZ1 TY8,
+            // 8 waves)
+            CFX_CONV_CASE(28, 1, 8, 32, 3, 512)
+            // 36: slab 3*10*34*36*4 = 147 KB + wtile 4.5 KB (TAPG 1)
+            CFX_CONV_CASE(36, 1, 8, 32, 1, 512)
+            // 48: slab 3*6*34*52*4 = 127 KB + wtile 9.2 KB (TZ1 TY4,
+            // 8 waves -> 1 m-tile per wave)
+            CFX_CONV_CASE(48, 1, 4, 32, 1, 512)
+            // 64: slab 3*6*18*68*4 = 86 KB + wtile 16.4 KB (TZ1 TY4 TX16;
+            // 8 waves x ... 1*4*1 = 4 tiles < 8 waves -> use 256 threads)
+            CFX_CONV_CASE(64, 2, 2, 16, 1, 256)
+            default:
+                g_err = "cfx_conv3_ndhwc: unsupported channel width";
+                return -1;
+        }
+    });
 #undef CFX_CONV_CASE
-    return 0;
 }
 
 namespace {
@@ -440,15 +438,13 @@ extern "C" int cfx_conv3_ndhwc_w32(cfx_ctx* ctx, const float* in,
         return -1;
     }
     dim3 grid((W + 31) / 32, (H + 7) / 8, (unsigned)(N * D));
-    hipEvent_t e0;
-    if (prof_begin(ctx, &e0)) return -1;
-    hipLaunchKernelGGL((k_conv3_w32<28, 28, 8, 3>), grid, dim3(512), 0,
-                       ctx->stream, in, wgt, bias, residual, out, N, D, H,
-                       W, do_elu);
-    CFX_CHECK(hipGetLastError());
     double flops = 2.0 * 27.0 * 28 * 28 * (double)N * D * H * W;
-    if (prof_end(ctx, e0, CFX_K_CONV, flops)) return -1;
-    return 0;
+    return cfx_timed(ctx, CFX_K_CONV, flops, [&] {
+        hipLaunchKernelGGL((k_conv3_w32<28, 28, 8, 3>), grid, dim3(512), 0,
+                           ctx->stream, in, wgt, bias, residual, out, N, D,
+                           H, W, do_elu);
+        return 0;
+    });
 }
 
 namespace {
@@ -1085,47 +1081,45 @@ extern "C" int cfx_conv3_ndhwc_zring(cfx_ctx* ctx, const float* in,
                                      int N, int D, int H, int W, int C,
                                      int K, int do_elu) {
     dim3 grid((W + 15) / 16, (H + 7) / 8, (unsigned)N);
-    hipEvent_t e0;
-    if (prof_begin(ctx, &e0)) return -1;
     // float4 wall staging needs 16-byte-aligned weight rows; otherwise the
     // ring takes its scalar staging loop
     const int wvec =
         (reinterpret_cast<uintptr_t>(wgt) % 16 == 0 && K % 4 == 0) ? 1 : 0;
-    if (C == 28 && K == 28) {
-        // wall holds both K tiles (96.8 KB + 60.5 KB ring). Three block
-        // tiles for columns 16..27 instead of the second tile measured
-        // slower (6.37 -> 6.61 ms)
-        hipLaunchKernelGGL((k_conv3_zring_pl<28, 28, 8, 16, 2, 0, 0>),
-                           grid, dim3(512), 0, ctx->stream, in, wgt, bias,
-                           residual, out, N, D, H, W, do_elu, 0, wvec);
-    } else if (C == 36 && K == 36) {
-        // the wall beside the ring holds one 16-wide K tile, so two
-        // launches: A = columns 0..15 plus 32..35 on a block tile out of
-        // the same staged planes, B = columns 16..31. The input re-read
-        // costs ~2x HBM traffic of a 113 MB activation per conv —
-        // negligible next to the compute
-        hipLaunchKernelGGL((k_conv3_zring_pl<36, 36, 8, 16, 1, 1, 32>),
-                           grid, dim3(512), 0, ctx->stream, in, wgt, bias,
-                           residual, out, N, D, H, W, do_elu, 0, wvec);
-        hipLaunchKernelGGL((k_conv3_zring_pl<36, 36, 8, 16, 1, 0, 0>),
-                           grid, dim3(512), 0, ctx->stream, in, wgt, bias,
-                           residual, out, N, D, H, W, do_elu, 16, wvec);
-    } else if (C == 48 && K == 48) {
-        // double-buffered per-dzi weight wall (full wall no longer fits
-        // beside the ring); one 16-wide K tile per launch
-        for (int j0 = 0; j0 < 48; j0 += 16) {
-            hipLaunchKernelGGL((k_conv3_zring_dw<48, 48, 8, 16>), grid,
-                               dim3(512), 0, ctx->stream, in, wgt, bias,
-                               residual, out, N, D, H, W, do_elu, j0);
-        }
-    } else {
-        g_err = "cfx_conv3_ndhwc_zring: width not instantiated";
-        return -1;
-    }
-    CFX_CHECK(hipGetLastError());
     double flops = 2.0 * 27.0 * C * K * (double)N * D * H * W;
-    if (prof_end(ctx, e0, CFX_K_CONV, flops)) return -1;
-    return 0;
+    return cfx_timed(ctx, CFX_K_CONV, flops, [&] {
+        if (C == 28 && K == 28) {
+            // wall holds both K tiles (96.8 KB + 60.5 KB ring). Three block
+            // tiles for columns 16..27 instead of the second tile measured
+            // slower (6.37 -> 6.61 ms)
+            hipLaunchKernelGGL((k_conv3_zring_pl<28, 28, 8, 16, 2, 0, 0>),
+                               grid, dim3(512), 0, ctx->stream, in, wgt, bias,
+                               residual, out, N, D, H, W, do_elu, 0, wvec);
+        } else if (C == 36 && K == 36) {
+            // the wall beside the ring holds one 16-wide K tile, so two
+            // launches: A = columns 0..15 plus 32..35 on a block tile out of
+            // the same staged planes, B = columns 16..31. The input re-read
+            // costs ~2x HBM traffic of a 113 MB activation per conv —
+            // negligible next to the compute
+            hipLaunchKernelGGL((k_conv3_zring_pl<36, 36, 8, 16, 1, 1, 32>),
+                               grid, dim3(512), 0, ctx->stream, in, wgt, bias,
+                               residual, out, N, D, H, W, do_elu, 0, wvec);
+            hipLaunchKernelGGL((k_conv3_zring_pl<36, 36, 8, 16, 1, 0, 0>),
+                               grid, dim3(512), 0, ctx->stream, in, wgt, bias,
+                               residual, out, N, D, H, W, do_elu, 16, wvec);
+        } else if (C == 48 && K == 48) {
+            // double-buffered per-dzi weight wall (full wall no longer fits
+            // beside the ring); one 16-wide K tile per launch
+            for (int j0 = 0; j0 < 48; j0 += 16) {
+                hipLaunchKernelGGL((k_conv3_zring_dw<48, 48, 8, 16>), grid,
+                                   dim3(512), 0, ctx->stream, in, wgt, bias,
+                                   residual, out, N, D, H, W, do_elu, j0);
+            }
+        } else {
+            g_err = "cfx_conv3_ndhwc_zring: width not instantiated";
+            return -1;
+        }
+        return 0;
+    });
 }
 
 namespace {
@@ -1638,45 +1632,40 @@ extern "C" int cfx_conv3_ndhwc_bf16(cfx_ctx* ctx, const void* in,
                                     const void* residual, void* out, int N,
                                     int D, int H, int W, int C, int K,
                                     int do_elu) {
-    if ((C == 36 && K == 36) || (C == 48 && K == 48)) {
-        // sliced schedule: (c-half, j-tile) x 4 launches; wgt pack is
-        // [27][64][48] zero-padded. Bias/ELU only on the final c-half,
-        // which chains through res = its own output.
-        dim3 grid((W + 31) / 32, (H + 7) / 8, (unsigned)N);
-        hipEvent_t e0;
-        if (prof_begin(ctx, &e0)) return -1;
-        const int CL2 = C - 32;
-        for (int j0 = 0; j0 < K; j0 += 32) {
-            hipLaunchKernelGGL((k_conv3_zring_bf16_s<32, 8, 32>), grid,
-                               dim3(512), 0, ctx->stream,
-                               (const cfx_bf16*)in, (const cfx_bf16*)wgt,
-                               nullptr, (const cfx_bf16*)residual,
-                               (cfx_bf16*)out, N, D, H, W, C, 32, 0, K, K,
-                               j0, 0);
-            hipLaunchKernelGGL((k_conv3_zring_bf16_s<16, 8, 32>), grid,
-                               dim3(512), 0, ctx->stream,
-                               (const cfx_bf16*)in, (const cfx_bf16*)wgt,
-                               bias, (const cfx_bf16*)out, (cfx_bf16*)out,
-                               N, D, H, W, C, CL2, 32, K, K, j0, do_elu);
-        }
-        CFX_CHECK(hipGetLastError());
-        double flops = 2.0 * 27.0 * C * K * (double)N * D * H * W;
-        if (prof_end(ctx, e0, CFX_K_CONV, flops)) return -1;
-        return 0;
-    }
-    if (C != 28 || K != 28) {
+    const bool sliced = (C == 36 && K == 36) || (C == 48 && K == 48);
+    if (!sliced && (C != 28 || K != 28)) {
         g_err = "cfx_conv3_ndhwc_bf16: only C == K == 28/36/48 instantiated";
         return -1;
     }
     dim3 grid((W + 31) / 32, (H + 7) / 8, (unsigned)N);
-    hipEvent_t e0;
-    if (prof_begin(ctx, &e0)) return -1;
-    hipLaunchKernelGGL((k_conv3_zring_bf16_a<28, 28, 8, 32>), grid,
-                       dim3(512), 0, ctx->stream, (const cfx_bf16*)in,
-                       (const cfx_bf16*)wgt, bias, (const cfx_bf16*)residual,
-                       (cfx_bf16*)out, N, D, H, W, do_elu);
-    CFX_CHECK(hipGetLastError());
-    double flops = 2.0 * 27.0 * 28 * 28 * (double)N * D * H * W;
-    if (prof_end(ctx, e0, CFX_K_CONV, flops)) return -1;
-    return 0;
+    double flops = 2.0 * 27.0 * C * K * (double)N * D * H * W;
+    return cfx_timed(ctx, CFX_K_CONV, flops, [&] {
+        if (sliced) {
+            // (c-half, j-tile) x 4 launches; wgt pack is [27][64][48]
+            // zero-padded. Bias/ELU only on the final c-half, which chains
+            // through res = its own output.
+            const int CL2 = C - 32;
+            for (int j0 = 0; j0 < K; j0 += 32) {
+                hipLaunchKernelGGL((k_conv3_zring_bf16_s<32, 8, 32>), grid,
+                                   dim3(512), 0, ctx->stream,
+                                   (const cfx_bf16*)in, (const cfx_bf16*)wgt,
+                                   nullptr, (const cfx_bf16*)residual,
+                                   (cfx_bf16*)out, N, D, H, W, C, 32, 0, K,
+                                   K, j0, 0);
+                hipLaunchKernelGGL((k_conv3_zring_bf16_s<16, 8, 32>), grid,
+                                   dim3(512), 0, ctx->stream,
+                                   (const cfx_bf16*)in, (const cfx_bf16*)wgt,
+                                   bias, (const cfx_bf16*)out,
+                                   (cfx_bf16*)out, N, D, H, W, C, CL2, 32, K,
+                                   K, j0, do_elu);
+            }
+        } else {
+            hipLaunchKernelGGL((k_conv3_zring_bf16_a<28, 28, 8, 32>), grid,
+                               dim3(512), 0, ctx->stream,
+                               (const cfx_bf16*)in, (const cfx_bf16*)wgt,
+                               bias, (const cfx_bf16*)residual,
+                               (cfx_bf16*)out, N, D, H, W, do_elu);
+        }
+        return 0;
+    });
 }

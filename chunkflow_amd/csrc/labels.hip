@@ -37,7 +37,9 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cstdint>
+#include <type_traits>
 
 #include "cfx_internal.h"
 // Table, table_insert / table_find, the status flags and their read-back
@@ -495,61 +497,56 @@ int check_volume(const int dims[3], int elem_bytes, const char* who,
     return 0;
 }
 
-template <typename T>
-int launch_run_starts(cfx_ctx* ctx, const T* in, long long n,
-                      unsigned long long* total) {
-    constexpr int SEG = SEG_BYTES / (int)sizeof(T);
-    long long head, body;
-    split_range(in, n, true, &head, &body);
+// The three parts of split_range in stream order: launch(vec, grid, begin,
+// end) is called for each non-empty one, `vec` a std::bool_constant that
+// picks the kernel. Head and body get one lane per `seg` voxels on at most
+// `cap` workgroups, the tail (less than one body segment) one workgroup.
+template <typename F>
+void launch_parts(long long head, long long body, long long n, int seg,
+                  int cap, F&& launch) {
     if (head > 0)
-        hipLaunchKernelGGL((k_run_starts<T, false>),
-                           dim3(std::min(grid_for((head + SEG - 1) / SEG),
-                                         kCountGrid)),
-                           dim3(kBlock), 0, ctx->stream, in, 0ll, head,
-                           total);
+        launch(std::false_type{},
+               std::min(grid_for((head + seg - 1) / seg), cap), 0ll, head);
     if (body > 0)
-        // one add per wave to a single word: keep the waves few
-        hipLaunchKernelGGL((k_run_starts<T, true>),
-                           dim3(std::min(grid_for(body / SEG), kCountGrid)),
-                           dim3(kBlock), 0,
-                           ctx->stream, in, head, head + body, total);
-    if (head + body < n)
-        hipLaunchKernelGGL((k_run_starts<T, false>), dim3(1), dim3(kBlock),
-                           0, ctx->stream, in, head + body, n, total);
-    CFX_CHECK(hipGetLastError());
-    return 0;
+        launch(std::true_type{}, std::min(grid_for(body / seg), cap), head,
+               head + body);
+    if (head + body < n) launch(std::false_type{}, 1, head + body, n);
 }
 
 template <typename T>
-int launch_count(cfx_ctx* ctx, const T* in, long long n, Table t,
-                 unsigned int* status) {
-    constexpr int SEG = SEG_BYTES / (int)sizeof(T);
+void launch_run_starts(cfx_ctx* ctx, const T* in, long long n,
+                       unsigned long long* total) {
     long long head, body;
     split_range(in, n, true, &head, &body);
-    if (head > 0)
-        hipLaunchKernelGGL((k_count<T, false>),
-                           dim3(std::min(grid_for((head + SEG - 1) / SEG),
-                                         kCountGrid)),
-                           dim3(kBlock), 0, ctx->stream, in, 0ll, head, t,
+    // one add per wave to a single word: keep the waves few
+    launch_parts(head, body, n, SEG_BYTES / (int)sizeof(T), kCountGrid,
+                 [&](auto vec, int grid, long long begin, long long end) {
+        hipLaunchKernelGGL((k_run_starts<T, decltype(vec)::value>),
+                           dim3(grid), dim3(kBlock), 0, ctx->stream, in,
+                           begin, end, total);
+    });
+}
+
+template <typename T>
+void launch_count(cfx_ctx* ctx, const T* in, long long n, Table t,
+                  unsigned int* status) {
+    long long head, body;
+    split_range(in, n, true, &head, &body);
+    // few, long-lived workgroups: each flushes its LDS table once
+    launch_parts(head, body, n, SEG_BYTES / (int)sizeof(T), kCountGrid,
+                 [&](auto vec, int grid, long long begin, long long end) {
+        hipLaunchKernelGGL((k_count<T, decltype(vec)::value>), dim3(grid),
+                           dim3(kBlock), 0, ctx->stream, in, begin, end, t,
                            status);
-    if (body > 0)
-        // few, long-lived workgroups: each flushes its LDS table once
-        hipLaunchKernelGGL((k_count<T, true>),
-                           dim3(std::min(grid_for(body / SEG), kCountGrid)),
-                           dim3(kBlock), 0, ctx->stream, in, head,
-                           head + body, t, status);
-    if (head + body < n)
-        hipLaunchKernelGGL((k_count<T, false>), dim3(1), dim3(kBlock), 0,
-                           ctx->stream, in, head + body, n, t, status);
-    CFX_CHECK(hipGetLastError());
-    return 0;
+    });
 }
 
 // the first h in [0, 4) at which seg + h and gt + h are both 16-byte aligned
 // starts the vector body; a pair of views with no such h is all scalar
 template <typename TS, typename TG>
-int launch_pair_count(cfx_ctx* ctx, const TS* seg, const TG* gt, long long n,
-                      Table ts, Table tg, Table t, unsigned int* status) {
+void launch_pair_count(cfx_ctx* ctx, const TS* seg, const TG* gt,
+                       long long n, Table ts, Table tg, Table t,
+                       unsigned int* status) {
     constexpr int SEG = PairGeom<TS, TG>::SEG;
     long long head = n, body = 0;
     for (long long h = 0; h < 4; ++h)
@@ -558,47 +555,26 @@ int launch_pair_count(cfx_ctx* ctx, const TS* seg, const TG* gt, long long n,
             body = (n - head) / SEG * SEG;
             break;
         }
-    if (head > 0)
-        hipLaunchKernelGGL((k_pair_count<TS, TG, false>),
-                           dim3(std::min(grid_for((head + SEG - 1) / SEG),
-                                         kCountGrid)),
-                           dim3(kBlock), 0, ctx->stream, seg, gt, 0ll, head,
-                           ts, tg, t, status);
-    if (body > 0)
-        hipLaunchKernelGGL((k_pair_count<TS, TG, true>),
-                           dim3(std::min(grid_for(body / SEG), kCountGrid)),
-                           dim3(kBlock), 0, ctx->stream, seg, gt, head,
-                           head + body, ts, tg, t, status);
-    if (head + body < n)
-        hipLaunchKernelGGL((k_pair_count<TS, TG, false>), dim3(1),
-                           dim3(kBlock), 0, ctx->stream, seg, gt,
-                           head + body, n, ts, tg, t, status);
-    CFX_CHECK(hipGetLastError());
-    return 0;
+    launch_parts(head, body, n, SEG, kCountGrid,
+                 [&](auto vec, int grid, long long begin, long long end) {
+        hipLaunchKernelGGL((k_pair_count<TS, TG, decltype(vec)::value>),
+                           dim3(grid), dim3(kBlock), 0, ctx->stream, seg, gt,
+                           begin, end, ts, tg, t, status);
+    });
 }
 
 template <typename T, int MODE>
-int launch_apply(cfx_ctx* ctx, const T* in, T* out, long long n, Table t,
-                 long long threshold) {
-    constexpr int SEG = SEG_BYTES / (int)sizeof(T);
+void launch_apply(cfx_ctx* ctx, const T* in, T* out, long long n, Table t,
+                  long long threshold) {
     long long head, body;
     split_range(in, n, misalign16(in) == misalign16(out), &head, &body);
-    if (head > 0)
-        hipLaunchKernelGGL((k_apply<T, false, MODE>),
-                           dim3(grid_for((head + SEG - 1) / SEG)),
-                           dim3(kBlock), 0, ctx->stream, in, out, 0ll, head,
-                           t, threshold);
-    if (body > 0)
-        hipLaunchKernelGGL((k_apply<T, true, MODE>),
-                           dim3(grid_for(body / SEG)), dim3(kBlock), 0,
-                           ctx->stream, in, out, head, head + body, t,
-                           threshold);
-    if (head + body < n)
-        hipLaunchKernelGGL((k_apply<T, false, MODE>), dim3(1), dim3(kBlock),
-                           0, ctx->stream, in, out, head + body, n, t,
-                           threshold);
-    CFX_CHECK(hipGetLastError());
-    return 0;
+    // no cap beyond grid_for's own
+    launch_parts(head, body, n, SEG_BYTES / (int)sizeof(T), INT_MAX,
+                 [&](auto vec, int grid, long long begin, long long end) {
+        hipLaunchKernelGGL((k_apply<T, decltype(vec)::value, MODE>),
+                           dim3(grid), dim3(kBlock), 0, ctx->stream, in, out,
+                           begin, end, t, threshold);
+    });
 }
 
 }  // namespace
@@ -610,17 +586,19 @@ extern "C" int cfx_label_run_starts(cfx_ctx* ctx, const void* labels,
     if (check_volume(dims, elem_bytes, "label_run_starts", &n)) return -1;
     unsigned long long* words;
     if (status_words(ctx, &words)) return -1;
-    hipEvent_t e0;
-    if (prof_begin(ctx, &e0)) return -1;
-    CFX_CHECK(hipMemsetAsync(words, 0, sizeof(unsigned long long),
-                             ctx->stream));
-    int rc = elem_bytes == 4
-        ? launch_run_starts(ctx, static_cast<const unsigned int*>(labels),
-                            n, words)
-        : launch_run_starts(
-              ctx, static_cast<const unsigned long long*>(labels), n, words);
+    int rc = cfx_timed(ctx, CFX_K_LABELS, (double)n * elem_bytes, [&] {
+        CFX_CHECK(hipMemsetAsync(words, 0, sizeof(unsigned long long),
+                                 ctx->stream));
+        if (elem_bytes == 4)
+            launch_run_starts(ctx, static_cast<const unsigned int*>(labels),
+                              n, words);
+        else
+            launch_run_starts(
+                ctx, static_cast<const unsigned long long*>(labels), n,
+                words);
+        return 0;
+    });
     if (rc) return rc;
-    if (prof_end(ctx, e0, CFX_K_LABELS, (double)n * elem_bytes)) return -1;
     unsigned long long total = 0;
     CFX_CHECK(hipMemcpyAsync(&total, words, sizeof(total),
                              hipMemcpyDeviceToHost, ctx->stream));
@@ -673,18 +651,19 @@ extern "C" int cfx_label_count(cfx_ctx* ctx, const void* labels,
     unsigned long long* words;
     if (status_words(ctx, &words)) return -1;
     unsigned int* status = reinterpret_cast<unsigned int*>(words + 1);
-    hipEvent_t e0;
-    if (prof_begin(ctx, &e0)) return -1;
-    CFX_CHECK(hipMemsetAsync(words + 1, 0, sizeof(unsigned long long),
-                             ctx->stream));
     Table t{keys, vals, (unsigned long long)capacity - 1};
-    int rc = elem_bytes == 4
-        ? launch_count(ctx, static_cast<const unsigned int*>(labels), n, t,
-                       status)
-        : launch_count(ctx, static_cast<const unsigned long long*>(labels),
-                       n, t, status);
+    int rc = cfx_timed(ctx, CFX_K_LABELS, (double)n * elem_bytes, [&] {
+        CFX_CHECK(hipMemsetAsync(words + 1, 0, sizeof(unsigned long long),
+                                 ctx->stream));
+        if (elem_bytes == 4)
+            launch_count(ctx, static_cast<const unsigned int*>(labels), n, t,
+                         status);
+        else
+            launch_count(ctx, static_cast<const unsigned long long*>(labels),
+                         n, t, status);
+        return 0;
+    });
     if (rc) return rc;
-    if (prof_end(ctx, e0, CFX_K_LABELS, (double)n * elem_bytes)) return -1;
     return read_status(ctx, words + 1, "label_count");
 }
 
@@ -719,10 +698,6 @@ extern "C" int cfx_label_pair_count(
     unsigned long long* words;
     if (status_words(ctx, &words)) return -1;
     unsigned int* status = reinterpret_cast<unsigned int*>(words + 1);
-    hipEvent_t e0;
-    if (prof_begin(ctx, &e0)) return -1;
-    CFX_CHECK(hipMemsetAsync(words + 1, 0, sizeof(unsigned long long),
-                             ctx->stream));
     Table ts{const_cast<unsigned long long*>(seg_keys), nullptr,
              (unsigned long long)seg_capacity - 1};
     Table tg{const_cast<unsigned long long*>(gt_keys), nullptr,
@@ -730,27 +705,29 @@ extern "C" int cfx_label_pair_count(
     Table t{keys, vals, (unsigned long long)capacity - 1};
     typedef unsigned int u32;
     typedef unsigned long long u64;
-    int rc;
-    if (seg_bytes == 4 && gt_bytes == 4)
-        rc = launch_pair_count(ctx, static_cast<const u32*>(seg),
-                               static_cast<const u32*>(gt), n, ts, tg, t,
-                               status);
-    else if (seg_bytes == 4)
-        rc = launch_pair_count(ctx, static_cast<const u32*>(seg),
-                               static_cast<const u64*>(gt), n, ts, tg, t,
-                               status);
-    else if (gt_bytes == 4)
-        rc = launch_pair_count(ctx, static_cast<const u64*>(seg),
-                               static_cast<const u32*>(gt), n, ts, tg, t,
-                               status);
-    else
-        rc = launch_pair_count(ctx, static_cast<const u64*>(seg),
-                               static_cast<const u64*>(gt), n, ts, tg, t,
-                               status);
+    double bytes = (double)n * (seg_bytes + gt_bytes);
+    int rc = cfx_timed(ctx, CFX_K_LABELS, bytes, [&] {
+        CFX_CHECK(hipMemsetAsync(words + 1, 0, sizeof(unsigned long long),
+                                 ctx->stream));
+        if (seg_bytes == 4 && gt_bytes == 4)
+            launch_pair_count(ctx, static_cast<const u32*>(seg),
+                              static_cast<const u32*>(gt), n, ts, tg, t,
+                              status);
+        else if (seg_bytes == 4)
+            launch_pair_count(ctx, static_cast<const u32*>(seg),
+                              static_cast<const u64*>(gt), n, ts, tg, t,
+                              status);
+        else if (gt_bytes == 4)
+            launch_pair_count(ctx, static_cast<const u64*>(seg),
+                              static_cast<const u32*>(gt), n, ts, tg, t,
+                              status);
+        else
+            launch_pair_count(ctx, static_cast<const u64*>(seg),
+                              static_cast<const u64*>(gt), n, ts, tg, t,
+                              status);
+        return 0;
+    });
     if (rc) return rc;
-    if (prof_end(ctx, e0, CFX_K_LABELS,
-                 (double)n * (seg_bytes + gt_bytes)))
-        return -1;
     return read_status(ctx, words + 1, who);
 }
 
@@ -770,29 +747,27 @@ extern "C" int cfx_label_mask(cfx_ctx* ctx, const void* in, void* out,
         g_err = "label_mask: null volume";
         return -1;
     }
-    hipEvent_t e0;
-    if (prof_begin(ctx, &e0)) return -1;
     Table t{const_cast<unsigned long long*>(keys),
             const_cast<unsigned int*>(vals),
             (unsigned long long)capacity - 1};
-    int rc;
-    if (elem_bytes == 4) {
-        auto* i4 = static_cast<const unsigned int*>(in);
-        auto* o4 = static_cast<unsigned int*>(out);
-        rc = mode == 0
-            ? launch_apply<unsigned int, 0>(ctx, i4, o4, n, t, threshold)
-            : launch_apply<unsigned int, 1>(ctx, i4, o4, n, t, threshold);
-    } else {
-        auto* i8 = static_cast<const unsigned long long*>(in);
-        auto* o8 = static_cast<unsigned long long*>(out);
-        rc = mode == 0
-            ? launch_apply<unsigned long long, 0>(ctx, i8, o8, n, t,
-                                                  threshold)
-            : launch_apply<unsigned long long, 1>(ctx, i8, o8, n, t,
-                                                  threshold);
-    }
-    if (rc) return rc;
-    if (prof_end(ctx, e0, CFX_K_LABELS, 2.0 * (double)n * elem_bytes))
-        return -1;
-    return 0;
+    return cfx_timed(ctx, CFX_K_LABELS, 2.0 * (double)n * elem_bytes, [&] {
+        if (elem_bytes == 4) {
+            auto* i4 = static_cast<const unsigned int*>(in);
+            auto* o4 = static_cast<unsigned int*>(out);
+            if (mode == 0)
+                launch_apply<unsigned int, 0>(ctx, i4, o4, n, t, threshold);
+            else
+                launch_apply<unsigned int, 1>(ctx, i4, o4, n, t, threshold);
+        } else {
+            auto* i8 = static_cast<const unsigned long long*>(in);
+            auto* o8 = static_cast<unsigned long long*>(out);
+            if (mode == 0)
+                launch_apply<unsigned long long, 0>(ctx, i8, o8, n, t,
+                                                    threshold);
+            else
+                launch_apply<unsigned long long, 1>(ctx, i8, o8, n, t,
+                                                    threshold);
+        }
+        return 0;
+    });
 }

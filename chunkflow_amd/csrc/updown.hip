@@ -1029,31 +1029,30 @@ extern "C" int cfx_conv155_out(cfx_ctx* ctx, const void* in,
         g_err = "cfx_conv155_out: too many workgroups for one grid axis";
         return -1;
     }
-    hipEvent_t e0;
-    if (prof_begin(ctx, &e0)) return -1;
     dim3 grid((W + CO_S - 1) / CO_S, (H + CO_R - 1) / CO_R,
               (unsigned)(N * D));
     const int vec_ok = W % 4 == 0 && ((size_t)out & 15) == 0;
-    if (is_bf16) {
-        // bf16 stays on the fixed tiles: 4 workgroups per CU there, and
-        // the y-walk measured slower (profiles/conv_in_mfma.json)
-        hipLaunchKernelGGL((k_conv155_out_mfma<cfx_bf16>), grid, dim3(256),
-                           0, ctx->stream, (const cfx_bf16*)in, wfrag, bias,
-                           (cfx_bf16*)out, H, W, vec_ok);
-    } else {
-        const int nxg = (W + CY_NW * CY_XO - 1) / (CY_NW * CY_XO);
-        const int nseg = (H + CY_YS - 1) / CY_YS;
-        const long long nwg = (long long)N * D * nseg * nxg;
-        if (nwg > 0)
-            hipLaunchKernelGGL(k_conv155_out_ywalk, dim3((unsigned)nwg),
-                               dim3(CY_NW * 64), 0, ctx->stream,
-                               (const float*)in, wfrag, bias, (float*)out, H,
-                               W, nxg, nseg, vec_ok);
-    }
-    CFX_CHECK(hipGetLastError());
     double flops = 2.0 * 25.0 * C * K * (double)N * D * H * W;
-    if (prof_end(ctx, e0, CFX_K_CONV_STREAM, flops)) return -1;
-    return 0;
+    return cfx_timed(ctx, CFX_K_CONV_STREAM, flops, [&] {
+        if (is_bf16) {
+            // bf16 stays on the fixed tiles: 4 workgroups per CU there, and
+            // the y-walk measured slower (profiles/conv_in_mfma.json)
+            hipLaunchKernelGGL((k_conv155_out_mfma<cfx_bf16>), grid,
+                               dim3(256), 0, ctx->stream,
+                               (const cfx_bf16*)in, wfrag, bias,
+                               (cfx_bf16*)out, H, W, vec_ok);
+        } else {
+            const int nxg = (W + CY_NW * CY_XO - 1) / (CY_NW * CY_XO);
+            const int nseg = (H + CY_YS - 1) / CY_YS;
+            const long long nwg = (long long)N * D * nseg * nxg;
+            if (nwg > 0)
+                hipLaunchKernelGGL(k_conv155_out_ywalk, dim3((unsigned)nwg),
+                                   dim3(CY_NW * 64), 0, ctx->stream,
+                                   (const float*)in, wfrag, bias,
+                                   (float*)out, H, W, nxg, nseg, vec_ok);
+        }
+        return 0;
+    });
 }
 
 extern "C" int cfx_conv155_c1(cfx_ctx* ctx, const void* in, const void* wgt,
@@ -1078,23 +1077,22 @@ extern "C" int cfx_conv155_c1(cfx_ctx* ctx, const void* in, const void* wgt,
     }
     if (nwg == 0) return 0;
     const int vec_ok = K % 4 == 0 && ((size_t)out & 15) == 0;
-    hipEvent_t e0;
-    if (prof_begin(ctx, &e0)) return -1;
-    if (is_bf16)
-        hipLaunchKernelGGL((k_conv155_in_mfma<cfx_bf16>),
-                           dim3((unsigned)nwg), dim3(CI_NW * 64), 0,
-                           ctx->stream, (const cfx_bf16*)in,
-                           (const cfx_bf16*)wgt, bias, (cfx_bf16*)out, H, W,
-                           K, nstrips, nrows, vec_ok);
-    else
-        hipLaunchKernelGGL((k_conv155_in_mfma<float>), dim3((unsigned)nwg),
-                           dim3(CI_NW * 64), 0, ctx->stream,
-                           (const float*)in, (const float*)wgt, bias,
-                           (float*)out, H, W, K, nstrips, nrows, vec_ok);
-    CFX_CHECK(hipGetLastError());
     double flops = 2.0 * 25.0 * K * (double)N * D * H * W;
-    if (prof_end(ctx, e0, CFX_K_CONV_STREAM, flops)) return -1;
-    return 0;
+    return cfx_timed(ctx, CFX_K_CONV_STREAM, flops, [&] {
+        if (is_bf16)
+            hipLaunchKernelGGL((k_conv155_in_mfma<cfx_bf16>),
+                               dim3((unsigned)nwg), dim3(CI_NW * 64), 0,
+                               ctx->stream, (const cfx_bf16*)in,
+                               (const cfx_bf16*)wgt, bias, (cfx_bf16*)out, H,
+                               W, K, nstrips, nrows, vec_ok);
+        else
+            hipLaunchKernelGGL((k_conv155_in_mfma<float>),
+                               dim3((unsigned)nwg), dim3(CI_NW * 64), 0,
+                               ctx->stream, (const float*)in,
+                               (const float*)wgt, bias, (float*)out, H, W, K,
+                               nstrips, nrows, vec_ok);
+        return 0;
+    });
 }
 
 namespace {
@@ -1136,7 +1134,6 @@ int um_launch_nt(cfx_ctx* ctx, const float* in, const float* wgt,
     hipLaunchKernelGGL((k_upconv2_mfma<NT, SKIP>), dim3(grid),
                        dim3(UM_NW * 64), shmem, ctx->stream, in, wgt, bias,
                        skip, out, W, C, xtiles, ntiles);
-    CFX_CHECK(hipGetLastError());
     return 0;
 }
 
@@ -1161,6 +1158,20 @@ int um_launch(cfx_ctx* ctx, const float* in, const float* wgt,
     return -1;
 }
 
+// the timed MFMA up-conv, with (SKIP) or without the skip-add epilogue;
+// zero tiles launch nothing and still push their row
+template <bool SKIP>
+int um_timed(cfx_ctx* ctx, const void* in, const void* wgt,
+             const float* bias, const void* skip, void* out, int N, int D,
+             int H, int W, int C, int K) {
+    double flops = 2.0 * 4.0 * C * K * (double)N * D * H * W;
+    return cfx_timed(ctx, CFX_K_CONV_STREAM, flops, [&] {
+        return um_launch<SKIP>(ctx, (const float*)in, (const float*)wgt,
+                               bias, (const float*)skip, (float*)out, N, D,
+                               H, W, C, K);
+    });
+}
+
 }  // namespace
 
 extern "C" int cfx_upconv_2x2_add(cfx_ctx* ctx, const void* in,
@@ -1179,14 +1190,7 @@ extern "C" int cfx_upconv_2x2_add(cfx_ctx* ctx, const void* in,
                 "C <= 64, K <= 48 and 16-byte aligned tensors";
         return -1;
     }
-    hipEvent_t e0;
-    if (prof_begin(ctx, &e0)) return -1;
-    if (um_launch<true>(ctx, (const float*)in, (const float*)wgt, bias,
-                        (const float*)skip, (float*)out, N, D, H, W, C, K))
-        return -1;
-    double flops = 2.0 * 4.0 * C * K * (double)N * D * H * W;
-    if (prof_end(ctx, e0, CFX_K_CONV_STREAM, flops)) return -1;
-    return 0;
+    return um_timed<true>(ctx, in, wgt, bias, skip, out, N, D, H, W, C, K);
 }
 
 extern "C" int cfx_upconv_2x2(cfx_ctx* ctx, const void* in, const void* wgt,
@@ -1196,35 +1200,27 @@ extern "C" int cfx_upconv_2x2(cfx_ctx* ctx, const void* in, const void* wgt,
         g_err = "cfx_upconv_2x2: C, K <= 64 supported";
         return -1;
     }
-    if (!is_bf16 && um_eligible(in, nullptr, out, N, D, H, W, C, K)) {
-        hipEvent_t e0;
-        if (prof_begin(ctx, &e0)) return -1;
-        if (um_launch<false>(ctx, (const float*)in, (const float*)wgt, bias,
-                             nullptr, (float*)out, N, D, H, W, C, K))
-            return -1;
-        double flops = 2.0 * 4.0 * C * K * (double)N * D * H * W;
-        if (prof_end(ctx, e0, CFX_K_CONV_STREAM, flops)) return -1;
-        return 0;
-    }
+    if (!is_bf16 && um_eligible(in, nullptr, out, N, D, H, W, C, K))
+        return um_timed<false>(ctx, in, wgt, bias, nullptr, out, N, D, H, W,
+                               C, K);
     constexpr int XI = 64;
     dim3 grid((W + XI - 1) / XI, H, (unsigned)(N * D));
     const size_t shmem =
         ((size_t)C * K * 4 + (size_t)XI * (C | 1)) * sizeof(float);
-    hipEvent_t e0;
-    if (prof_begin(ctx, &e0)) return -1;
-    if (is_bf16)
-        hipLaunchKernelGGL((k_upconv2<cfx_bf16, XI>), grid, dim3(256),
-                           shmem, ctx->stream, (const cfx_bf16*)in,
-                           (const cfx_bf16*)wgt, bias, (cfx_bf16*)out, N, D,
-                           H, W, C, K);
-    else
-        hipLaunchKernelGGL((k_upconv2<float, XI>), grid, dim3(256), shmem,
-                           ctx->stream, (const float*)in, (const float*)wgt,
-                           bias, (float*)out, N, D, H, W, C, K);
-    CFX_CHECK(hipGetLastError());
     double flops = 2.0 * 4.0 * C * K * (double)N * D * H * W;
-    if (prof_end(ctx, e0, CFX_K_CONV_STREAM, flops)) return -1;
-    return 0;
+    return cfx_timed(ctx, CFX_K_CONV_STREAM, flops, [&] {
+        if (is_bf16)
+            hipLaunchKernelGGL((k_upconv2<cfx_bf16, XI>), grid, dim3(256),
+                               shmem, ctx->stream, (const cfx_bf16*)in,
+                               (const cfx_bf16*)wgt, bias, (cfx_bf16*)out, N,
+                               D, H, W, C, K);
+        else
+            hipLaunchKernelGGL((k_upconv2<float, XI>), grid, dim3(256),
+                               shmem, ctx->stream, (const float*)in,
+                               (const float*)wgt, bias, (float*)out, N, D, H,
+                               W, C, K);
+        return 0;
+    });
 }
 
 extern "C" int cfx_downconv_2x2(cfx_ctx* ctx, const void* in,
@@ -1243,21 +1239,20 @@ extern "C" int cfx_downconv_2x2(cfx_ctx* ctx, const void* in,
     dim3 grid((W / 2 + XO - 1) / XO, H / 2, (unsigned)(N * D));
     const size_t shmem =
         ((size_t)C * K * 4 + (size_t)2 * 2 * XO * (C | 1)) * sizeof(float);
-    hipEvent_t e0;
-    if (prof_begin(ctx, &e0)) return -1;
-    if (is_bf16)
-        hipLaunchKernelGGL((k_downconv2<cfx_bf16, XO>), grid, dim3(256),
-                           shmem, ctx->stream, (const cfx_bf16*)in,
-                           (const cfx_bf16*)wgt, bias, (cfx_bf16*)out, N, D,
-                           H, W, C, K);
-    else
-        hipLaunchKernelGGL((k_downconv2<float, XO>), grid, dim3(256), shmem,
-                           ctx->stream, (const float*)in, (const float*)wgt,
-                           bias, (float*)out, N, D, H, W, C, K);
-    CFX_CHECK(hipGetLastError());
     double flops = 2.0 * 4.0 * C * K * (double)N * D * (H / 2) * (W / 2);
-    if (prof_end(ctx, e0, CFX_K_CONV_STREAM, flops)) return -1;
-    return 0;
+    return cfx_timed(ctx, CFX_K_CONV_STREAM, flops, [&] {
+        if (is_bf16)
+            hipLaunchKernelGGL((k_downconv2<cfx_bf16, XO>), grid, dim3(256),
+                               shmem, ctx->stream, (const cfx_bf16*)in,
+                               (const cfx_bf16*)wgt, bias, (cfx_bf16*)out, N,
+                               D, H, W, C, K);
+        else
+            hipLaunchKernelGGL((k_downconv2<float, XO>), grid, dim3(256),
+                               shmem, ctx->stream, (const float*)in,
+                               (const float*)wgt, bias, (float*)out, N, D, H,
+                               W, C, K);
+        return 0;
+    });
 }
 
 extern "C" int cfx_bias_res_elu(cfx_ctx* ctx, float* y, const float* bias,

@@ -293,27 +293,22 @@ extern "C" int cfx_affinity_fragments(cfx_ctx* ctx, const float* aff,
         return -1;
     }
     const int D = dims[0], H = dims[1], W = dims[2];
-    hipEvent_t e0;
-    if (prof_begin(ctx, &e0)) return -1;
-    hipLaunchKernelGGL(k_ws_init, dim3(grid_for(n)), dim3(kBlock), 0,
-                       ctx->stream, aff, D, H, W, low, high, labels,
-                       scratch);
-    hipLaunchKernelGGL(k_ws_merge, dim3(grid_for(n)), dim3(kBlock), 0,
-                       ctx->stream, scratch, D, H, W, labels);
-    hipLaunchKernelGGL(k_ws_compress, dim3(grid_for(n)), dim3(kBlock), 0,
-                       ctx->stream, labels, n);
-    if (cc_rank_roots(ctx, labels, n, scratch, n_components)) {
-        prof_drop(ctx, e0);
-        return -1;
-    }
-    hipLaunchKernelGGL(k_ws_final, dim3(grid_for(n)), dim3(kBlock), 0,
-                       ctx->stream, scratch, labels, n);
-    CFX_CHECK(hipGetLastError());
     // algorithmic bytes: the map once, the code word written and read, the
     // parent passes and the final gather as in cc.hip
     double bytes = (double)n * (12.0 + 8.0 + 4.0 * 6.0);
-    if (prof_end(ctx, e0, CFX_K_CC, bytes)) return -1;
-    return 0;
+    return cfx_timed(ctx, CFX_K_CC, bytes, [&] {
+        hipLaunchKernelGGL(k_ws_init, dim3(grid_for(n)), dim3(kBlock), 0,
+                           ctx->stream, aff, D, H, W, low, high, labels,
+                           scratch);
+        hipLaunchKernelGGL(k_ws_merge, dim3(grid_for(n)), dim3(kBlock), 0,
+                           ctx->stream, scratch, D, H, W, labels);
+        hipLaunchKernelGGL(k_ws_compress, dim3(grid_for(n)), dim3(kBlock), 0,
+                           ctx->stream, labels, n);
+        if (cc_rank_roots(ctx, labels, n, scratch, n_components)) return -1;
+        hipLaunchKernelGGL(k_ws_final, dim3(grid_for(n)), dim3(kBlock), 0,
+                           ctx->stream, scratch, labels, n);
+        return 0;
+    });
 }
 
 /* number of table operations cfx_region_graph will make on this volume: an
@@ -329,17 +324,18 @@ extern "C" int cfx_region_graph_runs(cfx_ctx* ctx, const unsigned int* frag,
     }
     unsigned long long* words;
     if (status_words(ctx, &words)) return -1;
-    hipEvent_t e0;
-    if (prof_begin(ctx, &e0)) return -1;
-    CFX_CHECK(hipMemsetAsync(words, 0, sizeof(unsigned long long),
-                             ctx->stream));
-    hipLaunchKernelGGL(k_region_edges<true>,
-                       dim3(grid_for((n + SEG - 1) / SEG, kRegionGrid)),
-                       dim3(kBlock), 0,
-                       ctx->stream, frag, nullptr, dims[0], dims[1], dims[2],
-                       Table{nullptr, nullptr, 0}, nullptr, words, nullptr);
-    CFX_CHECK(hipGetLastError());
-    if (prof_end(ctx, e0, CFX_K_LABELS, 4.0 * (double)n)) return -1;
+    int rc = cfx_timed(ctx, CFX_K_LABELS, 4.0 * (double)n, [&] {
+        CFX_CHECK(hipMemsetAsync(words, 0, sizeof(unsigned long long),
+                                 ctx->stream));
+        hipLaunchKernelGGL(k_region_edges<true>,
+                           dim3(grid_for((n + SEG - 1) / SEG, kRegionGrid)),
+                           dim3(kBlock), 0, ctx->stream, frag, nullptr,
+                           dims[0], dims[1], dims[2],
+                           Table{nullptr, nullptr, 0}, nullptr, words,
+                           nullptr);
+        return 0;
+    });
+    if (rc) return rc;
     unsigned long long total = 0;
     CFX_CHECK(hipMemcpyAsync(&total, words, sizeof(total),
                              hipMemcpyDeviceToHost, ctx->stream));
@@ -367,20 +363,19 @@ extern "C" int cfx_region_graph(cfx_ctx* ctx, const unsigned int* frag,
     unsigned long long* words;
     if (status_words(ctx, &words)) return -1;
     unsigned int* status = reinterpret_cast<unsigned int*>(words + 1);
-    hipEvent_t e0;
-    if (prof_begin(ctx, &e0)) return -1;
-    CFX_CHECK(hipMemsetAsync(words + 1, 0, sizeof(unsigned long long),
-                             ctx->stream));
-    hipLaunchKernelGGL(k_region_clear, dim3(grid_for(capacity)),
-                       dim3(kBlock), 0, ctx->stream, keys, counts, sums,
-                       capacity);
     Table t{keys, counts, (unsigned long long)capacity - 1};
-    hipLaunchKernelGGL(k_region_edges<false>,
-                       dim3(grid_for((n + SEG - 1) / SEG, kRegionGrid)),
-                       dim3(kBlock), 0,
-                       ctx->stream, frag, aff, dims[0], dims[1], dims[2], t,
-                       sums, nullptr, status);
-    CFX_CHECK(hipGetLastError());
-    if (prof_end(ctx, e0, CFX_K_LABELS, 4.0 * (double)n)) return -1;
+    int rc = cfx_timed(ctx, CFX_K_LABELS, 4.0 * (double)n, [&] {
+        CFX_CHECK(hipMemsetAsync(words + 1, 0, sizeof(unsigned long long),
+                                 ctx->stream));
+        hipLaunchKernelGGL(k_region_clear, dim3(grid_for(capacity)),
+                           dim3(kBlock), 0, ctx->stream, keys, counts, sums,
+                           capacity);
+        hipLaunchKernelGGL(k_region_edges<false>,
+                           dim3(grid_for((n + SEG - 1) / SEG, kRegionGrid)),
+                           dim3(kBlock), 0, ctx->stream, frag, aff, dims[0],
+                           dims[1], dims[2], t, sums, nullptr, status);
+        return 0;
+    });
+    if (rc) return rc;
     return read_status(ctx, words + 1, who);
 }
