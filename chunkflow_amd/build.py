@@ -8,7 +8,7 @@ CSRC = os.path.join(PKG_DIR, 'csrc')
 # the translation units, in the order of the hipcc line, and what they include
 SOURCES = [os.path.join(CSRC, name + '.hip')
            for name in ('cfx', 'cc', 'image', 'conv', 'updown', 'downsample',
-                        'labels', 'watershed')]
+                        'labels', 'watershed', 'filter')]
 HEADERS = [os.path.join(CSRC, 'cfx_internal.h'),
            os.path.join(CSRC, 'cc_unionfind.h'),
            os.path.join(CSRC, 'label_table.h'),

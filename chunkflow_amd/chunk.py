@@ -250,6 +250,14 @@ class Chunk:
         return Chunk(arr, voxel_offset=self.voxel_offset,
                      voxel_size=self.voxel_size)
 
+    def gaussian_filter_2d(self, sigma=1) -> 'Chunk':
+        """In-place gaussian blur of every (y,x) section
+        (chunk/base.py:846-853; rules and the per-channel difference on 4-D
+        chunks: chunkflow_amd/filters.py)."""
+        from .filters import gaussian_filter_2d
+        gaussian_filter_2d(self, sigma, inplace=True)
+        return self
+
     # --- arithmetic passthrough --------------------------------------------
     def __imul__(self, other):
         self.array *= other.array if isinstance(other, Chunk) else other

@@ -16,6 +16,8 @@ operators (reference chunkflow/flow/flow.py):
   evaluate-segmentation :1519-1542 (scores against a ground truth; gfx950
                                    contingency table on device chunks)
   normalize-contrast    :1672-1710 (device histogram/LUT kernels)
+  gaussian-filter       :1615-1630 (per-section blur, bit-exact to scipy;
+                                   gfx950 LDS-tile kernel on device chunks)
   load-h5 / save-h5     :976-1120  (in-repo HDF5 codec — h5io.py)
   load-tif / save-tif   :918-974   (in-repo TIFF codec — tiffio.py)
   log-summary           :1633-1647 (voxels/sec report shape)
@@ -223,6 +225,28 @@ def normalize_contrast(tasks, name, input_chunk_name, output_chunk_name,
                 chunk, lower_clip_fraction=lower_clip_fraction,
                 upper_clip_fraction=upper_clip_fraction, minval=minval,
                 maxval=maxval, per_section=per_section)
+            task['log']['timer'][name] = time() - start
+        yield task
+
+
+@main.command('gaussian-filter')
+@click.option('--name', type=str, default='gaussian-filter',
+              help='name of operator')
+@click.option('--input-chunk-name', '-i', type=str,
+              default=DEFAULT_CHUNK_NAME, help='input chunk name')
+@click.option('--sigma', '-s', type=click.INT, default=1,
+              help='standard deviation of gaussian kernel')
+@operator
+def gaussian_filter(tasks, name, input_chunk_name, sigma):
+    """Blur every (y,x) section of the chunk with a gaussian, in place."""
+    import torch
+    for task in tasks:
+        if task is not None:
+            start = time()
+            chunk = task[input_chunk_name]
+            if torch.cuda.is_available():
+                chunk = chunk.to_device()
+            task[input_chunk_name] = chunk.gaussian_filter_2d(sigma)
             task['log']['timer'][name] = time() - start
         yield task
 

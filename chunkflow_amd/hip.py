@@ -56,6 +56,8 @@ SIGNATURES = {
     'cfx_region_graph': (I, [P, P, P, P, P, P, P, L]),
     'cfx_hist_u8': (I, [P, P, L, I, P]),
     'cfx_lut_apply_u8': (I, [P, P, L, I, P]),
+    'cfx_gaussian2d': (I, [P, P, P, I, L, I, I, P, I, P, I]),
+    'cfx_median3d': (I, [P, P, P, I, L, P, P, I]),
     'cfx_downsample_avg_u8': (I, [P, P, P, I, P, P]),
     'cfx_downsample_avg_f32': (I, [P, P, P, I, P, P]),
     'cfx_downsample_mode2': (I, [P, P, P, I, P, I]),
@@ -367,6 +369,18 @@ class CfxContext:
 
     def lut_apply_u8(self, buf_ptr, n_per_sec, nsec, lut_ptr):
         self._call('cfx_lut_apply_u8', buf_ptr, n_per_sec, nsec, lut_ptr)
+
+    # --- image filters -------------------------------------------------------
+    def gaussian2d(self, in_ptr, out_ptr, is_f32, sections, height, width,
+                   wy_ptr, ry, wx_ptr, rx):
+        """wy_ptr / wx_ptr: device f64 weights (2*r+1 each), or None with
+        radius 0 to skip that axis"""
+        self._call('cfx_gaussian2d', in_ptr, out_ptr, bool(is_f32), sections,
+                   height, width, wy_ptr, ry, wx_ptr, rx)
+
+    def median3d(self, in_ptr, out_ptr, is_f32, volumes, dims, size, mode):
+        self._call('cfx_median3d', in_ptr, out_ptr, bool(is_f32), volumes,
+                   _i3(dims), _i3(size), mode)
 
     # --- downsample ----------------------------------------------------------
     def downsample_avg(self, in_ptr, out_ptr, channels, in_dims, factor,

@@ -180,6 +180,53 @@ class HipOps:
                                       t.element_size(), dims)
         return out
 
+    # --- image filters (semantics: chunkflow_amd/filters.py; kernels:
+    # csrc/filter.hip) ---------------------------------------------------------
+    def gaussian_filter_2d(self, t: torch.Tensor, sigma) -> torch.Tensor:
+        """Per-section 2-D gaussian of a uint8/float32 (z,y,x) or (C,z,y,x)
+        tensor, a new tensor."""
+        from .filters import check_gaussian_device
+        plan = check_gaussian_device(t.dtype, sigma)
+        if t.ndim not in (3, 4):
+            raise ValueError(f'gaussian_filter_2d: 3-D or 4-D only: '
+                             f'{tuple(t.shape)}')
+        t = t.contiguous()
+        out = torch.empty_like(t)
+        if t.numel() == 0:
+            return out
+        if plan[0] is None and plan[1] is None:
+            return out.copy_(t)
+        # the weights are scipy's float64 values, computed on the host
+        weights = [None if axis is None else
+                   torch.from_numpy(axis[1]).to(t.device) for axis in plan]
+        (wy, ry), (wx, rx) = [
+            (None, 0) if axis is None else (wt.data_ptr(), axis[0])
+            for axis, wt in zip(plan, weights)]
+        h, w = t.shape[-2:]
+        self.cfx.gaussian2d(t.data_ptr(), out.data_ptr(),
+                            t.dtype == torch.float32, t.numel() // (h * w),
+                            h, w, wy, ry, wx, rx)
+        return out
+
+    def median_filter(self, t: torch.Tensor, size=(3, 1, 1),
+                      mode: str = 'reflect') -> torch.Tensor:
+        """3-D median of a uint8/float32 (z,y,x) or (C,z,y,x) tensor (per
+        channel), a new tensor."""
+        from .filters import check_median_device
+        size, code = check_median_device(t.dtype, size, mode)
+        if t.ndim not in (3, 4):
+            raise ValueError(f'median_filter: 3-D or 4-D only: '
+                             f'{tuple(t.shape)}')
+        t = t.contiguous()
+        out = torch.empty_like(t)
+        if t.numel() == 0:
+            return out
+        self.cfx.median3d(t.data_ptr(), out.data_ptr(),
+                          t.dtype == torch.float32,
+                          1 if t.ndim == 3 else t.shape[0],
+                          tuple(t.shape[-3:]), size, code)
+        return out
+
     # --- label tables: per-label voxel counts and masking -------------------
     # (semantics: chunkflow_amd/segmentation.py; kernels: csrc/labels.hip)
     LABEL_TABLE_MIN = 64

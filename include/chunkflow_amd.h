@@ -16,6 +16,8 @@
  *   cfx_max                  <- inferencer.py:463-466 (assert < 1.0001)
  *   cfx_crop_margin          <- chunk/base.py:691-726 (flow.py:2053-2084)
  *   cfx_mask_using_last_channel <- chunk/base.py:685-689 (inferencer.py:468-477)
+ *   cfx_gaussian2d           <- chunk/base.py:846-853 (flow.py:1615-1630)
+ *   cfx_median3d             <- plugins/median_filter.py
  *
  * Conventions: the caller owns every buffer (device pointers come from
  * torch-ROCm tensors' data_ptr()); layout is contiguous C-order z-y-x with x
@@ -248,6 +250,32 @@ int cfx_hist_u8(cfx_ctx* ctx, const unsigned char* in, long long n_per_sec,
 /* in-place per-section LUT gather: buf[i] = lut[sec][buf[i]] */
 int cfx_lut_apply_u8(cfx_ctx* ctx, unsigned char* buf, long long n_per_sec,
                      int nsec, const unsigned char* lut);
+
+/* ---- image filters (gaussian-filter operator, median_filter plugin) ----- */
+/* Per-section 2-D gaussian of `sections` contiguous (height, width) images,
+ * uint8 or float32 (is_f32), bit-pinned to scipy.ndimage.gaussian_filter:
+ * the y pass, then the x pass, each t = v[i]*w[r], then for k = -r..-1
+ * t += (v[i+k] + v[i-k]) * w[k+r] in f64 with nothing fused, 'reflect'
+ * borders (d c b a | a b c d | d c b a, any radius against any length), and
+ * the result of EACH pass converted to the volume's dtype (f32 rounds to
+ * nearest, u8 truncates). wy / wx are DEVICE arrays of 2*r+1 normalised f64
+ * weights that the caller computes; the library never recomputes them. A
+ * NULL weight pointer with radius 0 skips that axis. Radii above 24 (the
+ * halo an LDS tile holds) are an error, never a wrong answer. in != out.
+ * Not timed into any profile slot. */
+int cfx_gaussian2d(cfx_ctx* ctx, const void* in, void* out, int is_f32,
+                   long long sections, int height, int width,
+                   const double* wy, int ry, const double* wx, int rx);
+/* 3-D median of `volumes` contiguous (D, H, W) volumes, uint8 or float32:
+ * the element of rank N/2 of the N = size[0]*size[1]*size[2] values of the
+ * window centred on each voxel, as scipy.ndimage.median_filter gives it.
+ * Every size entry is odd, N <= 125. mode: 0 reflect, 1 nearest, 2 mirror,
+ * 3 constant (value 0), 4 wrap, each with scipy's meaning. Float NaN and
+ * the sign of zero are out of contract. in != out. Not timed into any
+ * profile slot. */
+int cfx_median3d(cfx_ctx* ctx, const void* in, void* out, int is_f32,
+                 long long volumes, const int dims[3], const int size[3],
+                 int mode);
 
 /* ---- downsample (mip pyramid; the reference's downsample operator) ------ */
 /* Box average of a (channels, D, H, W) volume by factor[3] (z,y,x, any
